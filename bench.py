@@ -16,7 +16,13 @@ Precision (`--precision`, vae_trainer.PRECISION_POLICIES): the default mirrors t
 (encoder / LPIPS / discriminator at TF32-class operand precision or better, decoder bf16 as under its autocast);
 `bf16` is the all-bf16 throughput mode, reported beside it on the same line (`bf16_mode`).
 
-Extra objects on the JSON line:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set-up (model, resident batches, loss-scale
+calibration and the rehearsal of the timed steps), W warm-up steps, the N timed steps, then the JSON line (`value`, `ms_per_step`, ...).
+`--dump-outputs DIR` also writes what the LAST timed step returned to its caller (VAETrainStep.__call__'s dictionary: losses,
+reconstruction, latents, ...) as DIR/<name>.npy — the inputs are seeded, so two builds can be compared output for output.
+Everything else this file measures or checks runs only with `--full`, and is then unchanged.
+
+Extra objects on the JSON line (`--full`):
   roofline     — dominant kernel family (implicit-GEMM conv fwd/dgrad on MFMA): algorithmic FLOPs of every launch in the
                  timed region / their HIP-event durations, vs the dense MFMA peak; `wgrad` = the weight-gradient family,
                  `conv3x3` = the 3x3 conv GEMMs with >= 64 channels on both sides in all three passes (the north-star's 40 %
@@ -110,6 +116,12 @@ def parse(argv=None):
                          "per-GPU shapes the dispatch rules were NOT fitted on")
     ap.add_argument("--batch", type=int, default=0, help="per GPU (default: 16; 8 for c5)")
     ap.add_argument("--precision", default="", choices=[""] + list(DTYPE_NAMES), help="default: ref (c2 / c3), ref_vq (c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: instrumented + serial passes (roofline), HBM-family pass, fp16 report, comm, "
+                         "the other precisions, the configs[4] leg, CPU baseline and parity against the oracle (minutes); the --no-* options "
+                         "below trim that set")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the tensors the last timed step returned as DIR/<name>.npy (float32; integers as float64; at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-calibrate", action="store_true",
                     help="keep the default loss scales of the fp16 stacks (PMC passes under rocprofv3: traffic only, no timing claims)")
@@ -121,6 +133,10 @@ def parse(argv=None):
     ap.add_argument("--no-c5-leg", action="store_true", help="skip the configs[4] (VQ, 512x512) leg of the default line")
     ap.add_argument("--parity-mode-steps", type=int, default=5, help="timed steps of each `parity_mode` leg (fp32x6 / fp32x3 / ref3)")
     args = ap.parse_args(argv)
+    if not args.full:
+        if args.conv_table:
+            ap.error("--conv-table needs --full (the per-layer table is timed in the serial pass)")
+        args.no_cpu_baseline = args.no_secondary = args.no_c5_leg = True
     if not args.precision:
         args.precision = "ref_vq" if args.workload == "c5" else DEFAULT_PRECISION
     return args
@@ -227,12 +243,12 @@ def _median_time(fn, n):
     return statistics.median(ts)
 
 
-# What the restated loop that is timed here (`kind: "port"`: the GPU box has no /root/reference) was pinned against — to 2e-5 over three
-# optimizer steps, same ATen ops: tests/test_oracle.py::test_train_step_restatement_matches_reference_modules (runs wherever
-# /root/reference is mounted; tests/golden/*.npz are outputs of those modules, tests/golden/make_golden.py)
-REFERENCE_PIN = ("cloneofsimo/vqgan-training as mounted at /root/reference in the build container (a snapshot without .git, files dated "
-                 "2026-09-26; sha256[:16] ae.py 80e614adf9414229, utils.py 80d49ec4f8d5f97b, vae_trainer.py 266616fb3991bbe2), imported live by "
-                 "oracle/reference_import.py; pinned by tests/test_oracle.py::test_train_step_restatement_matches_reference_modules")
+# What the restated loop that is timed here (`kind: "port"`) was pinned against — to 2e-5 over three optimizer steps, same ATen ops:
+# tests/test_oracle.py::test_train_step_restatement_matches_reference_modules against the steps recorded from the reference's own
+# modules (tests/golden/train_step_ref_*.npz; like every tests/golden/*.npz an output of those modules, tests/golden/make_golden.py)
+REFERENCE_PIN = ("cloneofsimo/vqgan-training (a snapshot without .git, files dated 2026-09-26; sha256[:16] ae.py 80e614adf9414229, "
+                 "utils.py 80d49ec4f8d5f97b, vae_trainer.py 266616fb3991bbe2): three training steps of its own modules recorded in "
+                 "tests/golden/train_step_ref_*.npz; pinned by tests/test_oracle.py::test_train_step_restatement_matches_reference_modules")
 
 
 def cpu_baseline(args, cfg, configs0=True):
@@ -649,6 +665,36 @@ def scales_after_run(step, batch):
     return {"stacks": rows, "optimizer_steps_dropped": {"G": events["skipped_G"], "D": events["skipped_D"]}}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, path, budget=DUMP_BUDGET_BYTES):
+    """Every tensor of a step's output dictionary -> path/<name>.npy (float32; integer tensors float64), `budget` bytes at most in
+    all: when the whole would be larger, every tensor above 1 MB is cut down to a fixed sample (elements at sorted indices drawn
+    from numpy's default_rng(0), the same from run to run).  -> {name: [stored elements, elements]}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k in sorted(out):
+        v = out[k]
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach().cpu()
+        arrs[k] = v.to(torch.float32 if v.dtype.is_floating_point else torch.float64).contiguous().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    small = sum(a.nbytes for a in arrs.values() if a.nbytes <= 10 ** 6)
+    keep = 1.0 if total <= budget else max(budget - small, 0) / max(total - small, 1)
+    stored = {}
+    for k, a in arrs.items():
+        n = a.size
+        if keep < 1.0 and a.nbytes > 10 ** 6:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, size=int(n * keep)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        stored[k] = [int(a.size), int(n)]
+    return stored
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -874,7 +920,7 @@ def main():
     batches = [vq.vae_trainer.synthetic_batch(B, in_res, device, gen) for _ in range(4)]   # resident in HBM
     scales = [] if args.no_calibrate else calibrate(step, batches[0])      # [] unless the policy has fp16 stacks
     step.event_factory = _event
-    if world > 1:
+    if world > 1 and args.full:
         step.comm_events = []
     recal = []
     # The discriminator learns to tell uniform noise from reconstructions within a few steps (random-init VGG trunk, lr 2e-4): after the
@@ -930,12 +976,15 @@ def main():
     # same steps from the same state snapshot right after; the serial pass (one stream) follows that.  VQ_BENCH_TIMED_EVENTS=1 (tools'
     # A/B only) puts the brackets back into the timed region.
     # (--no-serial-pass, the profiler stages' short form, skips both extra passes: its roofline then comes from brackets in the timed region)
-    events_in_timed_region = os.environ.get("VQ_BENCH_TIMED_EVENTS", "0") == "1" or args.no_serial_pass
+    # A plain run (no --full) has neither the brackets nor the extra passes: `roofline` is null on its line.
+    events_in_timed_region = os.environ.get("VQ_BENCH_TIMED_EVENTS", "0") == "1" or (args.full and args.no_serial_pass)
     if not events_in_timed_region:
         ops.set_launch_hook(None)
     elapsed, last = timed_run(step, batches, args.steps, args.warmup, world, timer if events_in_timed_region else None,
                               recalibrate=after_warmup, trace=d_trace)
-    ops.set_launch_hook(timer.launch)
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    if args.full:
+        ops.set_launch_hook(timer.launch)
     timed_events = step.poll_range_events()               # (after the closing barrier of the timed region)
     if "rehearsed" in state:                              # the timed steps repeated the clean rehearsal (same state, scales, kernels)?
         rehearsal["repeated_by_the_timed_steps"] = state["rehearsed"] == d_trace
@@ -943,7 +992,7 @@ def main():
     if recal and recal[0]:
         scales = recal[0]                                 # the scales the timed steps ran under
     instr_elapsed = elapsed if events_in_timed_region else None
-    if not events_in_timed_region and not args.no_serial_pass:
+    if args.full and not events_in_timed_region and not args.no_serial_pass:
         # the instrumented repeat: same steps, same state, both streams live, every GEMM launch between two events
         timed_comm_events, step.comm_events = step.comm_events, None
         try:
@@ -953,7 +1002,7 @@ def main():
         finally:
             step.comm_events = timed_comm_events
     serial_timer, serial_elapsed = None, None
-    if not TEST_DEVICE and ops._wgrad_overlap and not args.no_serial_pass:
+    if args.full and not TEST_DEVICE and ops._wgrad_overlap and not args.no_serial_pass:
         # per-kernel durations need every kernel alone on the chip: the same steps once more on ONE stream (see `roofline.timing`)
         ops.set_wgrad_overlap(False)
         serial_timer = ConvTimer()
@@ -970,7 +1019,7 @@ def main():
     loss = float(last["overall_vae_loss"])
     assert loss == loss, "non-finite loss"
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         # `exposed`: what the compute stream waited for inside reducer.finish() over the timed steps (the warm-up's events
         # are dropped); `allreduce`: the same buckets reduced back to back with nothing to hide under.
         ev = step.comm_events[-2 * args.steps:] if cfg["gan"] else step.comm_events[-args.steps:]
@@ -1021,7 +1070,7 @@ def main():
         timer.records = timer.records[:mark]
     fp16_after = None
     try:                                                  # (every rank: the dry step holds the same collectives as a real one)
-        fp16_after = None if args.no_calibrate else scales_after_run(step, batches[0])   # (PMC passes: exactly steps + warmup steps)
+        fp16_after = None if args.no_calibrate or not args.full else scales_after_run(step, batches[0])   # (PMC passes: exactly steps + warmup steps)
     except Exception as exc:   # an auxiliary object must never cost the bench line
         fp16_after = {"error": repr(exc)}
     if world > 1:
@@ -1065,7 +1114,7 @@ def main():
             "metric": ("images/sec full train step (enc+VQ+dec+LPIPS+disc+bwd), 512x512 f=16" if cfg["vq"] else
                        f"images/sec full train step (area-resize+enc+HR-dec+LPIPS+disc+bwd), {in_res}x{in_res} batches, {cfg['res']}x{cfg['res']} encoder" if cfg.get("hr") else
                        "images/sec full train step (enc+dec+LPIPS+disc+bwd), 256x256 f=8"),
-            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": DTYPE_NAMES[args.precision],
             "data": f"synthetic uniform [-1,1] {in_res}x{in_res} RGB resident in HBM; random-init VAE (seed 42); random-init VGG16 "
@@ -1105,6 +1154,8 @@ def main():
             line["hbm"] = hbm
         if comm is not None:
             line["comm"] = comm
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "elements_stored_of": dumped}
 
     # ---- secondary legs on the same workload (fresh modules each; the primary step is released first):
     #   bf16_mode    the all-bf16 throughput mode

@@ -4,6 +4,9 @@ Run in the build container only:   python tests/golden/make_golden.py
 Inputs and weights are not stored: they are regenerated from oracle/weights.py (hash-based, machine
 independent); the fixtures hold only what the reference's own modules computed from them.
 """
+import glob
+import hashlib
+import json
 import os
 import sys
 
@@ -239,8 +242,126 @@ def photo_model_fixture():
     print("photo_models: lpips", val.flatten().tolist(), "logits", float(logits.abs().max()))
 
 
+# ---- what the tests that used to import the reference live now read instead (recorded from its own modules) ----------------------
+
+SURFACE_VAE_CFGS = ((32, 32, [1, 2], 1, 4), (64, 64, [1, 2, 4, 4], 2, 16))     # (resolution, ch, ch_mult, num_res_blocks, z_channels)
+SURFACE_TVAE = dict(resolution=16, in_channels=3, ch=32, out_ch=3, ch_mult=[1, 2, 2], num_res_blocks=2, z_channels=4)
+SURFACE_JSON = os.path.join(OUT, "reference_surface.json")
+
+
+def tensor_sha(t):
+    """sha256 of a tensor's bytes: two tensors of one dtype and shape are torch.equal iff these agree (no NaN / -0.0 in an initialiser)."""
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def surface(sd, values=False):
+    """State dict -> [[key, shape, dtype(, sha256 of the values)], ...] in the dict's own order."""
+    return [[k, list(v.shape), str(v.dtype).replace("torch.", "")] + ([tensor_sha(v)] if values else []) for k, v in sd.items()]
+
+
+def zeros_like_surface(rows):
+    """A state dict with the recorded keys, shapes and dtypes (what `oracle.weights.randomize_state_dict` needs of one)."""
+    return {r[0]: torch.zeros(r[1], dtype=getattr(torch, r[2])) for r in rows}
+
+
+def surface_fixture():
+    """reference_surface.json: keys, shapes, dtypes and — where the tests compare initial values — the sha256 of every tensor of the
+    reference's ae.VAE / utils.LPIPS / utils.PatchDiscriminator / tae.TVAE state dicts under the seeds the tests use."""
+    ae, utils, vt = RI.load()
+    tae = RI.load_tae()
+    out = {"vae_seed": 42, "vae": []}
+    for res, ch, mult, nrb, zc in SURFACE_VAE_CFGS:
+        torch.manual_seed(42)
+        out["vae"].append(surface(ae.VAE(res, 3, ch, 3, list(mult), nrb, zc, False, False, False).state_dict(), values=True))
+    out["lpips"] = surface(RI.in_ref_cwd(lambda: utils.LPIPS()).state_dict())
+    out["disc"] = surface(utils.PatchDiscriminator().state_dict())
+    out["vae_hr"] = surface(ae.VAE(32, 3, 32, 3, [1, 2], 1, 4, False, True, False).state_dict())
+    torch.manual_seed(7)
+    tv = tae.TVAE(**SURFACE_TVAE)
+    out["tvae_seed"] = 7
+    out["tvae"] = surface(tv.state_dict(), values=True)
+    out["tvae_decoder_z_shape"] = list(tv.decoder.z_shape)
+    out["tvae_encoder_mid_attn_head_dim"] = int(tv.encoder.mid.attn_1.head_dim)
+    with open(SURFACE_JSON, "w") as f:
+        json.dump(out, f, indent=0)
+    print("reference_surface:", {k: len(v) for k, v in out.items() if isinstance(v, list)})
+
+
+TRAIN_STEP_PREFIX = os.path.join(OUT, "train_step_ref")
+
+
+def _save_chunked(prefix, tensors, limit=900_000):
+    """{name: tensor} -> prefix_<i>.npz files of at most `limit` bytes of float32 each (committed files stay under 1 MiB)."""
+    for old in glob.glob(prefix + "_*.npz"):
+        os.remove(old)
+    chunk, size, n = {}, 0, 0
+    for k, v in list(tensors.items()) + [(None, None)]:
+        a = None if k is None else v.detach().numpy()
+        if chunk and (k is None or size + a.nbytes > limit):
+            np.savez_compressed(f"{prefix}_{n}.npz", **chunk)
+            chunk, size, n = {}, 0, n + 1
+        if k is not None:
+            chunk[k] = a
+            size += a.nbytes
+    return n
+
+
+def load_chunked(prefix):
+    out = {}
+    for path in sorted(glob.glob(prefix + "_*.npz")):
+        with np.load(path) as g:
+            out.update({k: torch.from_numpy(g[k]) for k in g.files})
+    return out
+
+
+def train_step_fixture():
+    """Three optimizer steps of the training loop assembled from the reference's own modules and functions (vae_trainer.py:525-708 with
+    world_size 1, LPIPS eval, hinge GAN; loop body restated literally): the logged losses of every step, the VAE gradients of the
+    first step (before AdamW) and the VAE parameters after the third — tests/test_oracle.py runs the oracle's restated step on the
+    same seeded weights and batch against them."""
+    ae, utils, vt = RI.load()
+    res, ch, mult = 32, 32, [1, 2]
+    torch.manual_seed(0)
+    vae = ae.VAE(res, 3, ch, 3, list(mult), 1, 4, False, False, False)
+    vae.load_state_dict(W.randomize_state_dict(vae.state_dict(), 1))
+    lp = RI.in_ref_cwd(lambda: utils.LPIPS().eval())
+    lp.load_state_dict(W.randomize_state_dict(lp.state_dict(), 2, relu_net=True))
+    disc = utils.PatchDiscriminator()
+    disc.load_state_dict(W.randomize_state_dict(disc.state_dict(), 4, relu_net=True))
+    x = W.image_batch(2, res, seed=8)
+    opt_g = torch.optim.AdamW([{"params": [p for n, p in vae.named_parameters() if "conv_in" not in n], "lr": 1e-2 / ch},
+                               {"params": [p for n, p in vae.named_parameters() if "conv_in" in n], "lr": 1e-4}],
+                              weight_decay=1e-3, betas=(0.9, 0.95))
+    opt_d = torch.optim.AdamW(disc.parameters(), lr=2e-4, weight_decay=1e-3, betas=(0.9, 0.95))
+    from transformers import get_cosine_schedule_with_warmup
+    sched = get_cosine_schedule_with_warmup(opt_g, 2, 10)
+    outs_ref, ref_grads = [], None
+    for it in range(3):
+        z = vae.encoder(x); zs = vae.reg(z); rec = vae.decoder(zs)
+        rp, fp = disc(x), disc(rec.detach())
+        d_loss, ar, af, acc = vt.gan_disc_loss(rp, fp, "hinge")
+        opt_d.zero_grad(); d_loss.mean().backward(retain_graph=True); opt_d.step()
+        percep = lp(vt.gradnorm(rec), x).mean()
+        vloss, _ = vt.vae_loss_function(x, vt.gradnorm(rec, weight=0.001), z)
+        g_gan = -disc(vt.gradnorm(rec, weight=1.0)).mean()
+        overall = percep + g_gan + vloss
+        overall.backward()
+        if it == 0:
+            ref_grads = {n: p.grad.clone() for n, p in vae.named_parameters()}
+        opt_g.step(); opt_g.zero_grad(); sched.step(); opt_d.zero_grad()
+        outs_ref.append((overall.item(), percep.item(), d_loss.item()))
+    _save_chunked(TRAIN_STEP_PREFIX + "_grads", ref_grads)
+    _save_chunked(TRAIN_STEP_PREFIX + "_params", dict(vae.state_dict()))
+    np.savez(TRAIN_STEP_PREFIX + "_losses.npz", losses=np.array(outs_ref, dtype=np.float64))
+    print("train_step_ref: losses", outs_ref)
+
+
 if __name__ == "__main__":
     only = sys.argv[1:]
+    if not only or "surface" in only:
+        surface_fixture()
+    if not only or "train_step" in only:
+        train_step_fixture()
     if "photos" in only:            # (only on request: needs /root/reference/contents and PIL)
         photo_fixture()
     if not only or "photo_models" in only:

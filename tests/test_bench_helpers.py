@@ -104,3 +104,42 @@ def test_traffic_file_is_only_trusted_for_these_sources_this_precision_and_this_
     (tmp_path / "profiles" / "r3_traffic.json").write_text(json.dumps(dict(good, workload="c5", igemm_family_bytes_per_launch=999)))
     assert b.load_traffic("ref", "c5")[0]["igemm_family_bytes_per_launch"] == 999
     assert b.load_traffic("ref", "c3")[0]["igemm_family_bytes_per_launch"] == 214
+
+
+def test_plain_run_is_the_default_and_full_brings_the_rest_back(monkeypatch):
+    """Without --full every leg beside the headline is off (and --conv-table, which needs the serial pass, is refused); with it the
+    --no-* options decide as before."""
+    import pytest
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and (a.steps, a.warmup) == (7, 2)
+    assert a.no_cpu_baseline and a.no_secondary and a.no_c5_leg
+    a = b.parse(["--full"])
+    assert a.full and not (a.no_cpu_baseline or a.no_secondary or a.no_c5_leg or a.no_serial_pass)
+    a = b.parse(["--full", "--no-secondary", "--conv-table", "t.txt"])
+    assert a.no_secondary and not a.no_cpu_baseline and a.conv_table == "t.txt"
+    with pytest.raises(SystemExit):
+        b.parse(["--conv-table", "t.txt"])
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every tensor of the step's dictionary as <name>.npy, float32 (integers float64), non-tensors left out; over the
+    budget the large tensors shrink to the same seeded sample on every call, the small ones stay whole."""
+    import numpy as np
+    import torch
+    b = _bench()
+    out = {"reconstructed": torch.arange(600_000, dtype=torch.float32).reshape(2, 3, 100, 1000).to(torch.bfloat16),
+           "indices": torch.arange(12, dtype=torch.int64).reshape(3, 4), "loss": torch.tensor(1.5), "note": "not a tensor"}
+    stored = b.dump_outputs(out, str(tmp_path / "a"))
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["indices.npy", "loss.npy", "reconstructed.npy"]
+    rec = np.load(tmp_path / "a" / "reconstructed.npy")
+    assert rec.dtype == np.float32 and rec.shape == (2, 3, 100, 1000) and stored["reconstructed"] == [600_000, 600_000]
+    assert np.array_equal(rec, out["reconstructed"].float().numpy())
+    assert np.load(tmp_path / "a" / "indices.npy").dtype == np.float64 and float(np.load(tmp_path / "a" / "loss.npy")) == 1.5
+    for d in ("b", "c"):
+        stored = b.dump_outputs(out, str(tmp_path / d), budget=1_200_000)
+    small, cut = np.load(tmp_path / "c" / "indices.npy"), np.load(tmp_path / "c" / "reconstructed.npy")
+    assert small.shape == (3, 4) and cut.ndim == 1 and 200_000 < cut.size == stored["reconstructed"][0] < 300_000
+    assert sum(np.load(p).nbytes for p in (tmp_path / "c").iterdir()) <= 1_200_000
+    assert np.array_equal(cut, np.load(tmp_path / "b" / "reconstructed.npy"))
+    assert set(cut.tolist()) <= set(rec.reshape(-1).tolist())

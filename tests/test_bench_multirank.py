@@ -1,4 +1,4 @@
-"""bench.py END TO END with two ranks before the first multi-GPU run on hardware: `python bench.py --gpus 2` on the test-only device
+"""bench.py END TO END with two ranks before the first multi-GPU run on hardware: `python bench.py --full --gpus 2` on the test-only device
 switch (VQ_BENCH_TEST_DEVICE=emu: host cores, the fiber-emulator build of the kernel sources, gloo) and a toy configuration.  Every
 rank-gated branch of main() runs — the self-launch under torch.distributed.run (the reference's launcher.sh:3-9 is a torchrun line),
 fp16 loss-scale calibration rounds (all ranks the same number), the timed region with its barriers and the MAX over ranks, the `comm`
@@ -26,7 +26,7 @@ def two_rank_line(emu_library):
                VQ_BENCH_TEST_CFG=json.dumps({"ch": 32, "ch_mult": [1, 2], "z": 4, "res": 16, "batch": 1, "calibrate_rounds": 1,
                                              "hbm_steps": 1, "secondary_steps": 1}))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload",
                         "c3" if GAN else "c2"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -199,41 +199,24 @@ def test_conv_fwd_dgrad_wgrad(backend, case):
 
 
 # The binary16 instantiations of the 16-bit kernels (same sources, `DT` template parameter): every bf16 case again with fp16
-# storage on the GPU; the emulator runs one case per kernel family (generic / LDS-DMA with LDS and register weights / patch
-# data gradient / three-tap and LDS-DMA weight gradients / the 8-channel image kernels / phase-decomposed forms).
+# storage, on both backends (generic / LDS-DMA with LDS and register weights / patch data gradient / three-tap and LDS-DMA weight
+# gradients / the 8-channel image kernels / phase-decomposed forms).
 FP16_CONV_CASES = [("fp16",) + c[1:] for c in CONV_CASES if c[0] == "bf16"]
-_FP16_ON_EMU = {("fp16",) + c for c in [
-    (1, 8, 8, 16, 32, 3, 1, 1, 1, False, None), (2, 6, 6, 128, 72, 3, 1, 1, 1, True, None), (1, 8, 8, 64, 64, 4, 4, 0, 1, False, None),
-    (1, 8, 8, 64, 128, 3, 2, 0, 1, False, (4, 4)), (1, 8, 8, 256, 256, 3, 1, 1, 1, False, None), (1, 16, 16, 128, 128, 3, 1, 1, 1, False, None),
-    (2, 4, 8, 256, 512, 1, 1, 0, 1, False, None), (2, 8, 64, 3, 64, 3, 1, 1, 1, True, None), (1, 4, 64, 128, 3, 3, 1, 1, 1, False, None),
-    (1, 4, 4, 64, 256, 3, 1, 1, 2, False, None), (2, 4, 12, 128, 64, 3, 2, 0, 1, False, (2, 6)), (1, 4, 16, 64, 96, 3, 1, 1, 1, True, None)]}
-assert _FP16_ON_EMU <= set(FP16_CONV_CASES)
 
 
 @pytest.mark.parametrize("case", FP16_CONV_CASES, ids=lambda c: "-".join(map(str, c)))
 def test_conv_fp16_storage(backend, case):
-    if backend.name == "emu" and case not in _FP16_ON_EMU:
-        pytest.skip("binary16 twin of a bf16 case: on the GPU only")
     _conv_case(backend, case)
 
 
 # The VQ_F16X2 instantiations (two binary16 pieces per value, three MFMAs per product; policy "f16x3"): every 16-bit and fp32x3 case
-# again in that storage on the GPU — same kernels, `DT` template parameter; the weight gradients of the three-tap shapes in the native
-# three-product form (round 6), the others through the virtual-channel form and wgrad_reduce_x2_kernel; the emulator runs one case per
-# kernel family.
+# again in that storage, on both backends — same kernels, `DT` template parameter; the weight gradients of the three-tap shapes in the native
+# three-product form (round 6), the others through the virtual-channel form and wgrad_reduce_x2_kernel.
 F16X3_CONV_CASES = sorted({("f16x3",) + c[1:] for c in CONV_CASES if c[0] in ("bf16", "fp32x3")}, key=repr)
-_F16X3_ON_EMU = {("f16x3",) + c for c in [
-    (1, 8, 8, 16, 32, 3, 1, 1, 1, False, None), (2, 6, 6, 128, 72, 3, 1, 1, 1, True, None), (1, 8, 8, 64, 64, 4, 4, 0, 1, False, None),
-    (1, 8, 8, 64, 128, 3, 2, 0, 1, False, (4, 4)), (1, 8, 8, 128, 128, 3, 1, 1, 1, False, None), (1, 8, 8, 72, 8, 1, 1, 0, 1, False, None),
-    (1, 8, 8, 3, 64, 3, 1, 1, 1, True, None), (1, 4, 4, 24, 1, 2, 2, 0, 1, False, None), (1, 4, 4, 64, 64, 3, 1, 1, 2, False, None),
-    (1, 4, 16, 64, 96, 3, 1, 1, 1, True, None), (1, 8, 8, 8, 24, 3, 2, 0, 1, False, (4, 4))]}
-assert _F16X3_ON_EMU <= set(F16X3_CONV_CASES)
 
 
 @pytest.mark.parametrize("case", F16X3_CONV_CASES, ids=lambda c: "-".join(map(str, c)))
 def test_conv_f16x3_storage(backend, case):
-    if backend.name == "emu" and case not in _F16X3_ON_EMU:
-        pytest.skip("VQ_F16X2 twin of a 16-bit / fp32x3 case: on the GPU only")
     _conv_case(backend, case)
 
 
@@ -246,8 +229,6 @@ def test_conv_f16x3_forced_kernels(backend, case, mode):
     weight tiles, 3 = the 256 x 256 tile — patch-staged where the shape allows, + 512 << 4 its one-tap ping-pong form —, 5 = nine-tap,
     6 = one-tap only, 7 = three-tap, 9 = weights through LDS): 32 real channels = one virtual chunk, 64 = two; ReLU, the sub-pixel
     Upsample (S = 2 patch kernel), a 1x1; forward + both gradients."""
-    if backend.name == "emu" and (mode not in (3, 5, 7) or case[4] != 64 or case[9] == 2):
-        pytest.skip("on the GPU only (emulator time)")
     with hinted(conv=mode):
         _conv_case(backend, case)
 
@@ -267,8 +248,10 @@ def test_wgrad_f16x3_native_three_product(backend, case, wgrad_hint):
     four waves, fragments = the hi / lo piece of 32 real channels, one accumulator per tap, real-channel slabs, the ordinary split
     reduction) instead of running on the virtual 2C x 2C problem with the quadrant sum behind it (kernel_hint bit 3 = 8 keeps that form
     for the A/B); so does the one-tap LDS-DMA kernel on its 128- and 256-wide tiles (conv_wgrad_glds_kernel<..., X3 = 1>).  Both forms against the fp32 oracle at the f16x3 tolerance: dw, the fused bias gradient, and — same launches — y / dx."""
-    if backend.name == "emu" and (case[2] * case[3] > 1024 or (case[3] * case[2] > 256 and wgrad_hint == 8)):
-        pytest.skip("larger case: on the GPU only")
+    if backend.name == "emu" and case[2] * case[3] > 1024:
+        # (run there once, 45-55 s each: dw / y / dx within tolerance, the fused bias gradient — an fp32 sum over 131072 pixels in the
+        # emulator's block order — at 1.03e-5 against the 1e-5 bound the GPU meets; needs the device's reduction order)
+        pytest.skip("256 x 256 images: needs the GPU")
     with hinted(wgrad=wgrad_hint):
         _conv_case(backend, case)
 
@@ -411,8 +394,8 @@ def test_wgrad_lds_dma_tiles(backend, bt, prec):
     shift as a template parameter: rows of 16 / 32 / >= 64 pixels = SEG 4 / 5 / 6) with the two waves of a SIMD staging the next
     chunk half a chunk apart; 16 = every wave stages right after the chunk barrier; 64 / 128 / 256 = each one-tap LDS-DMA tile
     (4 / 4 / 8 waves); 1 = the 4 B/lane split reduction."""
-    if prec == "fp16" and bt not in (0, 16):
-        pytest.skip("binary16 twins of the two forms of the three-tap kernel only")
+    if backend.name == "gpu" and prec == "fp16" and bt not in (0, 16):
+        pytest.skip("binary16 twins of the two forms of the three-tap kernel only (the other hints: on the emulator)")
     with hinted(wgrad=bt):
         _conv_case(backend, (prec, 1, 8, 16, 256, 256, 3, 1, 1, 1, False, None))      # rows of 16 pixels (SEG 4), two cin tiles
         _conv_case(backend, (prec, 3, 8, 16, 128, 128, 3, 1, 1, 1, False, None))      # 6 chunks in one split
@@ -1070,8 +1053,6 @@ def test_groupnorm_statistics_from_the_conv_epilogue(backend, prec_name, Ci, Co,
     """The epilogue of a convolution that feeds an FP32GroupNorm reduces that norm's statistics from its fp32 accumulators
     (vq_conv2d_fwd gn_partials + vq_gn_stats_finalize); they must equal the separate statistics pass over the stored tensor up
     to the storage rounding, the normalised output must match, and with the knob off nothing rides on the tensor."""
-    if backend.name == "emu" and hw > 16:
-        pytest.skip("larger case: on the GPU only")
     big_tile = (Ci, Co, hw, k) in ((64, 256, 16, 3), (32, 256, 16, 3))
     with hinted(conv=3 if big_tile else 0):             # 3: the patch-staged 256 x 256 tile at a small shape, 8 partial rows per tile
         _gn_epilogue_case(backend, prec_name, Ci, Co, hw, k)
@@ -1170,8 +1151,6 @@ def test_patch_staged_256_tile(backend, case, dbg):
     tile knob 3 at emulator-sized shapes: several patches per image, 1-3 channel chunks, image borders on every side of a patch,
     ReLU / residual-free epilogues, the nearest-2x gather, forward + both gradients (the data gradient of the first three cases
     runs the same kernel with Cout = Cin of the layer: a partial 256-row tile)."""
-    if backend.name == "emu" and case[4] == 192 and dbg == 512:
-        pytest.skip("the one-tap twin of the largest case: on the GPU only")
     with hinted(conv=3 + (dbg << 4)):
         _conv_case(backend, case)
 

@@ -1,11 +1,9 @@
-"""Pins the oracle (oracle/*.py restatement) — CPU only.
-
- 1. against the committed golden fixtures, which were produced by the reference's own modules
-    (tests/golden/make_golden.py) — runs everywhere;
- 2. against the reference imported live from /root/reference — runs only where it is mounted
-    (the build container), on additional configurations.
+"""Pins the oracle (oracle/*.py restatement) — CPU only — against the committed golden fixtures, which were produced by the
+reference's own modules (tests/golden/make_golden.py): forward / backward vectors, the state-dict surface (keys, shapes, initial
+values) and a three-step training trajectory.  Nothing outside the repository is read.
 The reference ships no golden vectors or known-answer tests of its own.
 """
+import json
 import os
 
 import numpy as np
@@ -14,10 +12,10 @@ import torch
 
 from oracle import model_ref as M
 from oracle import ops_ref as R
-from oracle import reference_import as RI
 from oracle import weights as W
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+from golden import make_golden as G  # noqa: E402
 from golden.make_golden import VAE_CFGS, cfg_fields  # noqa: E402
 
 
@@ -99,70 +97,56 @@ def test_loss_restatements_match_golden():
     assert close(R.gradnorm_backward(gg, 0.5), g["gradnorm"], 1e-6)
 
 
-needs_ref = pytest.mark.skipif(not RI.available(), reason="/root/reference is only mounted in the build container")
+def _reference_surface():
+    with open(G.SURFACE_JSON) as f:
+        return json.load(f)
 
 
-@needs_ref
+def _shapes(rows):
+    return {r[0]: tuple(r[1]) for r in rows}
+
+
 def test_state_dict_surface_matches_reference():
-    """Same keys, shapes and (under the same seed) the same initial values as ae.VAE / utils.* ."""
+    """Same keys, shapes and (under the same seed) the same initial values as ae.VAE / utils.* : against the surface recorded from
+    the reference's own modules (tests/golden/reference_surface.json; initial values by the sha256 of every tensor)."""
     import vqgan_training_amd as vq
-    ae, utils, vt = RI.load()
-    for cfg in ((32, 32, [1, 2], 1, 4), (64, 64, [1, 2, 4, 4], 2, 16)):
+    ref_all = _reference_surface()
+    for cfg, ref in zip(G.SURFACE_VAE_CFGS, ref_all["vae"]):
         res, ch, mult, nrb, zc = cfg
-        torch.manual_seed(42)
-        ref = ae.VAE(res, 3, ch, 3, list(mult), nrb, zc, False, False, False).state_dict()
-        torch.manual_seed(42)
+        torch.manual_seed(ref_all["vae_seed"])
         ours = vq.ae.VAE(res, 3, ch, 3, list(mult), nrb, zc, False, False, False).state_dict()
-        assert list(ref) == list(ours)
-        for k in ref:
-            assert torch.equal(ref[k], ours[k]), k
-    ref_l = RI.in_ref_cwd(lambda: utils.LPIPS()).state_dict()
+        assert [r[0] for r in ref] == list(ours)
+        for k, shape, dtype, sha in ref:
+            assert tuple(ours[k].shape) == tuple(shape) and str(ours[k].dtype) == "torch." + dtype, k
+            assert G.tensor_sha(ours[k]) == sha, k
     our_l = vq.utils.LPIPS(pretrained_path=None).state_dict()
-    assert {k: tuple(v.shape) for k, v in ref_l.items()} == {k: tuple(v.shape) for k, v in our_l.items()}
-    ref_d = utils.PatchDiscriminator().state_dict()
+    assert _shapes(ref_all["lpips"]) == {k: tuple(v.shape) for k, v in our_l.items()}
     our_d = vq.utils.PatchDiscriminator().state_dict()
-    assert {k: tuple(v.shape) for k, v in ref_d.items()} == {k: tuple(v.shape) for k, v in our_d.items()}
-    hr = ae.VAE(32, 3, 32, 3, [1, 2], 1, 4, False, True, False).state_dict()
+    assert _shapes(ref_all["disc"]) == {k: tuple(v.shape) for k, v in our_d.items()}
     ours_hr = vq.ae.VAE(32, 3, 32, 3, [1, 2], 1, 4, False, True, False).state_dict()
-    assert {k: tuple(v.shape) for k, v in hr.items()} == {k: tuple(v.shape) for k, v in ours_hr.items()}
+    assert _shapes(ref_all["vae_hr"]) == {k: tuple(v.shape) for k, v in ours_hr.items()}
 
 
-@needs_ref
 def test_train_step_restatement_matches_reference_modules():
-    """One restated step (oracle) vs the same step assembled from the reference's own modules/functions
-    (vae_trainer.py:525-708 with world_size 1, LPIPS eval, hinge GAN)."""
-    ae, utils, vt = RI.load()
-    res, ch, mult = 32, 32, [1, 2]
-    torch.manual_seed(0)
-    vae = ae.VAE(res, 3, ch, 3, list(mult), 1, 4, False, False, False)
-    vae.load_state_dict(W.randomize_state_dict(vae.state_dict(), 1))
-    lp = RI.in_ref_cwd(lambda: utils.LPIPS().eval())
-    lp.load_state_dict(W.randomize_state_dict(lp.state_dict(), 2, relu_net=True))
-    disc = utils.PatchDiscriminator()
-    disc.load_state_dict(W.randomize_state_dict(disc.state_dict(), 4, relu_net=True))
-    st = M.RefState(vae.state_dict(), lp.state_dict(), disc.state_dict())
+    """Three restated steps (oracle) vs the same steps assembled from the reference's own modules/functions
+    (vae_trainer.py:525-708 with world_size 1, LPIPS eval, hinge GAN), recorded by tests/golden/make_golden.py train_step_fixture:
+    same seeded weights (key names and shapes from the recorded surface) and batch."""
+    ref_all = _reference_surface()
+    res, ch = 32, 32
+    assert tuple(G.SURFACE_VAE_CFGS[0]) == (res, ch, [1, 2], 1, 4)
+    # (LPIPS / discriminator: this package's modules supply the constant buffers — ScalingLayer, BatchNorm statistics — that the
+    # re-randomisation keeps; their surface is the reference's: test_state_dict_surface_matches_reference)
+    import vqgan_training_amd as vq
+    st = M.RefState(W.randomize_state_dict(G.zeros_like_surface(ref_all["vae"][0]), 1),
+                    W.randomize_state_dict(vq.utils.LPIPS(pretrained_path=None).state_dict(), 2, relu_net=True),
+                    W.randomize_state_dict(vq.utils.PatchDiscriminator().state_dict(), 4, relu_net=True))
     x = W.image_batch(2, res, seed=8)
-    # --- reference modules, loop body restated literally
-    opt_g = torch.optim.AdamW([{"params": [p for n, p in vae.named_parameters() if "conv_in" not in n], "lr": 1e-2 / ch},
-                               {"params": [p for n, p in vae.named_parameters() if "conv_in" in n], "lr": 1e-4}],
-                              weight_decay=1e-3, betas=(0.9, 0.95))
-    opt_d = torch.optim.AdamW(disc.parameters(), lr=2e-4, weight_decay=1e-3, betas=(0.9, 0.95))
-    from transformers import get_cosine_schedule_with_warmup
-    sched = get_cosine_schedule_with_warmup(opt_g, 2, 10)
-    outs_ref, outs = [], []
+    outs_ref = np.load(G.TRAIN_STEP_PREFIX + "_losses.npz")["losses"]
+    ref_grads = G.load_chunked(G.TRAIN_STEP_PREFIX + "_grads")
+    ref_params = G.load_chunked(G.TRAIN_STEP_PREFIX + "_params")
+    assert outs_ref.shape == (3, 3) and set(ref_params) == set(st.vae) and set(ref_grads) <= set(ref_params) and len(ref_grads) > 50
+    outs = []
     for it in range(3):
-        z = vae.encoder(x); zs = vae.reg(z); rec = vae.decoder(zs)
-        rp, fp = disc(x), disc(rec.detach())
-        d_loss, ar, af, acc = vt.gan_disc_loss(rp, fp, "hinge")
-        opt_d.zero_grad(); d_loss.mean().backward(retain_graph=True); opt_d.step()
-        percep = lp(vt.gradnorm(rec), x).mean()
-        vloss, _ = vt.vae_loss_function(x, vt.gradnorm(rec, weight=0.001), z)
-        g_gan = -disc(vt.gradnorm(rec, weight=1.0)).mean()
-        overall = percep + g_gan + vloss
-        overall.backward()
-        ref_grads = {n: p.grad.clone() for n, p in vae.named_parameters()}
-        opt_g.step(); opt_g.zero_grad(); sched.step(); opt_d.zero_grad()
-        outs_ref.append((overall.item(), percep.item(), d_loss.item()))
         o = M.train_step_ref(st, x, do_ganloss=True, disc_type="hinge", learning_rate_vae=1e-2, vae_ch=ch,
                              max_steps=10, warmup_steps=2)
         outs.append((o["overall_vae_loss"].item(), o["perceptual_loss"].item(), o["d_loss"].item()))
@@ -174,30 +158,32 @@ def test_train_step_restatement_matches_reference_modules():
                 assert (o["grads"][k] - g).abs().max().item() < 1e-4 * gmax, k
     # steps 2 and 3 run on the updated parameters: the losses pin optimizer + schedule + D update
     assert close(torch.tensor(outs), torch.tensor(outs_ref), 2e-5)
-    for k, v in vae.state_dict().items():
+    for k, v in ref_params.items():
         assert (st.vae[k] - v).abs().max().item() < 2.5e-3, k      # bounded by 3 Adam steps of <= lr
 
 
-@needs_ref
 def test_checkpoints_interchange_with_reference(tmp_path):
-    """N4 wire formats both ways: our bf16 safetensors export loads strict into the reference VAE().bfloat16()
-    (README.hf.md:38-40), and a reference-side `module.`-prefixed torch checkpoint (vae_trainer.py:903-907) loads into ours."""
+    """N4 wire formats both ways: our bf16 safetensors export holds exactly the reference VAE's state-dict surface in bfloat16 — what
+    a strict load into the reference's VAE().bfloat16() (README.hf.md:38-40) needs — and a reference-side `module.`-prefixed torch
+    checkpoint (vae_trainer.py:903-907; keys and shapes from the recorded surface) loads into ours."""
     import vqgan_training_amd as vq
     from safetensors.torch import load_file
-    ae, utils, vt = RI.load()
+    ref_rows = _reference_surface()["vae"][0]
     args = (32, 3, 32, 3, [1, 2], 1, 4, False, False, False)
+    assert tuple(G.SURFACE_VAE_CFGS[0]) == (args[0], args[2], args[4], args[5], args[6])
     ours = vq.ae.VAE(*args[:4], list(args[4]), *args[5:])
     ours.load_state_dict(W.randomize_state_dict(ours.state_dict(), 1))
     path = str(tmp_path / "x_bf16.pt")
     vq.vae_trainer.export_bf16_safetensors(ours, path)
-    ref = ae.VAE(*args[:4], list(args[4]), *args[5:]).bfloat16()
-    ref.load_state_dict(load_file(path))                                   # strict
-    for k, v in ref.state_dict().items():
-        assert torch.equal(v, ours.state_dict()[k].to(torch.bfloat16)), k
-    ref32 = ae.VAE(*args[:4], list(args[4]), *args[5:])
-    ref32.load_state_dict(W.randomize_state_dict(ref32.state_dict(), 7))
+    wire = load_file(path)
+    assert set(wire) == {r[0] for r in ref_rows}                           # strict: no missing, no unexpected key
+    for k, shape, dtype, _sha in ref_rows:
+        want = torch.bfloat16 if getattr(torch, dtype).is_floating_point else getattr(torch, dtype)
+        assert tuple(wire[k].shape) == tuple(shape) and wire[k].dtype == want, k
+        assert torch.equal(wire[k], ours.state_dict()[k].to(want)), k
+    ref32 = W.randomize_state_dict(G.zeros_like_surface(ref_rows), 7)
     p2 = str(tmp_path / "ref.pt")
-    torch.save({"module." + k: v for k, v in ref32.state_dict().items()}, p2)
+    torch.save({"module." + k: v for k, v in ref32.items()}, p2)
     vq.vae_trainer.load_checkpoint(ours, p2)
     for k, v in ours.state_dict().items():
-        assert torch.equal(v, ref32.state_dict()[k]), k
+        assert torch.equal(v, ref32[k]), k

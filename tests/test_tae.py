@@ -1,7 +1,7 @@
 """The 3-D TVAE (reference tae.py) on the HIP path.
 
-  * oracle (oracle/tae_ref.py) vs the golden fixtures the reference's own tae.TVAE produced (tests/golden/tvae_*.npz) and,
-    where /root/reference is mounted, vs the reference module live — including the state-dict surface;
+  * oracle (oracle/tae_ref.py) vs the golden fixtures the reference's own tae.TVAE produced (tests/golden/tvae_*.npz), and the
+    state-dict surface of the HIP modules vs the one recorded from the reference module (tests/golden/reference_surface.json);
   * the HIP modules (vqgan-training_amd/tae.py) vs the same fixtures: forward and gradients in the fp32-class parity
     mode, forward in bf16 throughput mode;
   * ops.conv3d alone vs F.conv3d for the three layer kinds, with batch > 1 and odd frame counts (per-sample temporal
@@ -16,9 +16,9 @@ import torch.nn.functional as F
 
 import vqgan_training_amd as vq
 from vqgan_training_amd import ops
-from oracle import reference_import as RI
 from oracle import tae_ref as T
 from oracle import weights as W
+from golden import make_golden as G
 from golden.make_golden import TVAE_CFGS, tvae_inputs
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -49,23 +49,23 @@ def test_oracle_matches_reference_golden(name):
             assert rel(p[k[5:]].grad, g[k]) < 1e-4, k
 
 
-@pytest.mark.skipif(not RI.available(), reason="/root/reference is only mounted in the build container")
 def test_state_dict_surface_and_init_match_reference():
     """Same keys, shapes and — under the same seed — the same initial values as tae.TVAE (parameter creation order and
-    initialisers, tae.py:13-23,60-81,123-170,189-224), and strict loading both ways."""
-    tae = RI.load_tae()
-    kw = dict(resolution=16, in_channels=3, ch=32, out_ch=3, ch_mult=[1, 2, 2], num_res_blocks=2, z_channels=4)
-    torch.manual_seed(7)
-    ref = tae.TVAE(**kw)
-    torch.manual_seed(7)
-    ours = vq.tae.TVAE(**kw)
-    rs, os_ = ref.state_dict(), ours.state_dict()
-    assert list(rs) == list(os_)
-    for k in rs:
-        assert rs[k].shape == os_[k].shape and torch.equal(rs[k], os_[k]), k
-    ref.load_state_dict(os_, strict=True)
-    ours.load_state_dict(rs, strict=True)
-    assert ours.decoder.z_shape == ref.decoder.z_shape and ours.encoder.mid.attn_1.head_dim == ref.encoder.mid.attn_1.head_dim
+    initialisers, tae.py:13-23,60-81,123-170,189-224), and strict loading: against the surface recorded from the reference's module
+    (tests/golden/reference_surface.json; initial values by the sha256 of every tensor)."""
+    import json
+    with open(G.SURFACE_JSON) as f:
+        ref_all = json.load(f)
+    ref = ref_all["tvae"]
+    torch.manual_seed(ref_all["tvae_seed"])
+    ours = vq.tae.TVAE(**G.SURFACE_TVAE)
+    os_ = ours.state_dict()
+    assert [r[0] for r in ref] == list(os_)
+    for k, shape, dtype, sha in ref:
+        assert tuple(shape) == tuple(os_[k].shape) and "torch." + dtype == str(os_[k].dtype) and G.tensor_sha(os_[k]) == sha, k
+    ours.load_state_dict(W.randomize_state_dict(G.zeros_like_surface(ref), seed=3), strict=True)
+    assert list(ours.decoder.z_shape) == ref_all["tvae_decoder_z_shape"]
+    assert ours.encoder.mid.attn_1.head_dim == ref_all["tvae_encoder_mid_attn_head_dim"]
 
 
 @pytest.mark.parametrize("name", list(TVAE_CFGS))
