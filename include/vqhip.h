@@ -392,6 +392,40 @@ int vq_vq_scatter_add(const float* gq, const int64_t* idx, int64_t n_tokens, int
                       float* dcodebook, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * EMA codebook (ABI 11; NOT in the reference — the usual VQ-VAE / VQGAN recipe).  The codebook is trained without an optimizer:
+ * per step, with n_k = tokens on code k and s_k = their sum (over ALL ranks),
+ *     N_k <- g N_k + (1-g) n_k ;  m_k <- g m_k + (1-g) s_k ;  T = sum N ;  Ns_k = (N_k + eps) / (T + K eps) * T ;  e_k = m_k / Ns_k
+ * evaluated in double from the fp32 state (N = cluster_size [K], m = embed_sum [K][D]) and EXACT integer statistics; N, m and e are
+ * each rounded to fp32 once, e from the unrounded m and Ns; T is summed in a fixed order.
+ * The statistics are integers: int64 counts [K] followed by int64 fixed-point sums [K][D] — the first 8 * K * (D + 1) bytes of the
+ * workspace — at the power-of-two scale 2^(60 - ceil(log2 n_global) - e), 2^e > `amax` >= max |token| over all ranks (the scale of
+ * vq_vq_scatter_add; `amax` is a DEVICE float the caller measures, e.g. vq_absmax, and MAX-reduces over ranks).  Integer sums do
+ * not depend on the order of the tokens, and the accumulators of several ranks add up (int64 SUM all-reduce of those bytes, between
+ * accumulate and update) to exactly the statistics of one process holding the whole batch: N, m and the codebook are
+ * bit-reproducible under any token order and any split of a batch over ranks.  The rest of the workspace is the update's scratch. */
+size_t vq_vq_ema_workspace(int n_codes, int dim);
+/* Zeroes the accumulators, then one pass over this rank's n_tokens tokens [n_tokens][dim] and their codes idx (entries outside
+ * [0, n_codes) are ignored).  n_global = tokens of the whole batch over all ranks (sizes the fixed-point scale). */
+int vq_vq_ema_accumulate(const float* tokens, const int64_t* idx, int64_t n_tokens, int64_t n_global, int n_codes, int dim,
+                         const float* amax, void* workspace, size_t ws_bytes, void* stream);
+/* The update above, from the (all-reduced) accumulators; n_global and amax as given to accumulate.  usage (may be NULL): 2 DEVICE
+ * floats = { perplexity exp(-sum p log p) with p = n_k / sum n, number of codes with n_k > 0 } of this step's statistics. */
+int vq_vq_ema_update(void* workspace, size_t ws_bytes, int64_t n_global, const float* amax, int n_codes, int dim, double decay,
+                     double eps, float* cluster_size, float* embed_sum, float* codebook, float* usage, void* stream);
+/* Reseeding of dead codes (N_k < threshold; threshold = +inf: every code — initialisation from data) with tokens of the batch:
+ *     e_k = m_k = token[g_k],  N_k = 1,     g_k = splitmix64(splitmix64(seed + step) + k) mod n_global
+ *     splitmix64(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *                     return x ^ (x >> 31)          (unsigned 64-bit arithmetic)
+ * Global token g lives on the rank whose tokens are [token_offset, token_offset + n_local).  Two phases, because the picked token may
+ * live on another rank:  phase 0 writes candidates [K][D] — the picked token's row for the dead codes whose token this rank holds,
+ * zeros elsewhere (so a float SUM all-reduce over ranks moves every row intact: one non-zero contributor) — and changes no state;
+ * phase 1 installs the candidate rows of the dead codes and resets their N and m (tokens / n_local / token_offset / n_global / step /
+ * seed are not read).  N is identical on every rank, so every rank derives the same dead set on the device: no host readback. */
+int vq_vq_ema_reseed(int phase, float* cluster_size, float threshold, int64_t step, uint64_t seed, const float* tokens,
+                     int64_t n_local, int64_t token_offset, int64_t n_global, int n_codes, int dim, float* candidates,
+                     float* embed_sum, float* codebook, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware-layout probe (one wave, one MFMA / LDS transpose read, raw per-lane dump); used by
  * tests/test_hw_layout.py to pin the gfx950 register layouts the kernels assume.
  * which: 0 = mfma_f32_32x32x16_bf16, 1 = mfma_f32_16x16x32_bf16, 2 = ds_read_b64_tr_b16, 3 = mfma_f32_32x32x16_f16, 4 = v_permlane32_swap_b32,

@@ -16,7 +16,7 @@ VQ_BF16 = 0
 VQ_F32 = 1
 VQ_F16 = 2
 VQ_F16X2 = 3      # two binary16 pieces per value (hi, lo), carried by torch.complex32 tensors: 4 bytes per element, same shapes
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libvqhip.so")
@@ -56,6 +56,7 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
+_D = C.c_double
 _Z = C.c_size_t
 _U64 = C.c_uint64
 _DP = C.POINTER(VqConvDesc)
@@ -110,6 +111,10 @@ _SIGNATURES = {
     "vq_vq_nearest_fwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "vq_vq_scatter_workspace": (_Z, [_I, _I]),
     "vq_vq_scatter_add": (_I, [_P, _P, _L, _I, _I, _P, _P, _Z, _P]),
+    "vq_vq_ema_workspace": (_Z, [_I, _I]),
+    "vq_vq_ema_accumulate": (_I, [_P, _P, _L, _L, _I, _I, _P, _P, _Z, _P]),
+    "vq_vq_ema_update": (_I, [_P, _Z, _L, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
+    "vq_vq_ema_reseed": (_I, [_I, _P, _F, _L, _U64, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P]),
     "vq_debug_probe": (_I, [_I, _P, _P, _P]),
 }
 

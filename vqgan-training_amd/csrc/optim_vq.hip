@@ -438,3 +438,215 @@ extern "C" int vq_vq_scatter_add(const float* gq, const int64_t* idx, int64_t n_
   VQ_CHECK_LAUNCH("vq_vq_scatter_add");
   return VQ_OK;
 }
+
+// ------------------------------------------------------------------------------------------ VQ: EMA codebook
+// Exponential-moving-average codebook training (include/vqhip.h "EMA codebook").  The per-step statistics — tokens per
+// code and their sums — are accumulated as 64-bit integers (counts) and 64-bit FIXED POINT (sums, vq_fixed_scale as in the scatter-add
+// above): integer addition is associative, so the atomics may land in any order AND the partial statistics of several ranks add up
+// (an int64 SUM all-reduce) to exactly what one process would have counted over the whole batch.  The update then reads nothing but
+// the fp32 state and those integers, in double, and rounds every stored value to fp32 once.
+// Accumulator layout (the first 8 * n_codes * (dim + 1) bytes of the workspace — what the host all-reduces): int64 counts [K], then
+// int64 sums [K][D]; the update's scratch follows: the unrounded new cluster sizes (double [K]) and 4 doubles per block of 256 codes.
+static constexpr int VQ_EMA_BLOCK = 256;
+static inline size_t vq_ema_acc_bytes(int n_codes, int dim) { return (size_t)n_codes * ((size_t)dim + 1) * 8; }
+extern "C" size_t vq_vq_ema_workspace(int n_codes, int dim) {
+  if (n_codes <= 0 || dim <= 0) return 0;
+  return vq_ema_acc_bytes(n_codes, dim) + (size_t)n_codes * 8 + (size_t)vq_ceil_div(n_codes, VQ_EMA_BLOCK) * 4 * 8 + 64;
+}
+
+// lanes run along `dim`: one wave instruction adds one contiguous segment of 64 / D rows (256 B of a row pair at D = 32)
+__global__ __launch_bounds__(256) void vq_ema_accumulate_kernel(const float* __restrict__ tok, const int64_t* __restrict__ idx,
+                                                                 int64_t n_tokens, int64_t n_global, int n_codes, int dim,
+                                                                 const float* __restrict__ amax, unsigned long long* __restrict__ counts,
+                                                                 unsigned long long* __restrict__ sums) {
+  const double scale = vq_fixed_scale(*amax, n_global);
+  const int64_t total = n_tokens * dim;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = i / dim;
+    const int k = (int)(i - t * dim);
+    const int64_t code = idx[t];
+    if (code >= 0 && code < n_codes) {
+      const long long q = (long long)rint((double)tok[i] * scale);
+      atomicAdd(sums + code * dim + k, (unsigned long long)q);               // two's complement: wraps like signed addition
+      if (k == 0) atomicAdd(counts + code, 1ull);
+    }
+  }
+}
+
+extern "C" int vq_vq_ema_accumulate(const float* tokens, const int64_t* idx, int64_t n_tokens, int64_t n_global, int n_codes, int dim,
+                                    const float* amax, void* workspace, size_t ws_bytes, void* stream) {
+  VQ_REQUIRE(tokens && idx && amax && workspace, VQ_ERR_INVALID, "vq_vq_ema_accumulate: null pointer");
+  VQ_REQUIRE(n_codes > 0 && dim > 0 && n_tokens > 0 && n_global >= n_tokens, VQ_ERR_INVALID,
+             "vq_vq_ema_accumulate: empty problem, or n_global < n_tokens (n_tokens=%lld n_global=%lld n_codes=%d dim=%d)",
+             (long long)n_tokens, (long long)n_global, n_codes, dim);
+  VQ_REQUIRE(ws_bytes >= vq_vq_ema_workspace(n_codes, dim), VQ_ERR_WORKSPACE, "vq_vq_ema_accumulate: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(workspace, 0, vq_ema_acc_bytes(n_codes, dim), s);
+  if (e != hipSuccess) { vq_set_error("vq_vq_ema_accumulate: hipMemsetAsync: %s", hipGetErrorString(e)); return VQ_ERR_HIP; }
+  unsigned long long* counts = (unsigned long long*)workspace;
+  int64_t b = vq_ceil_div(n_tokens * dim, 256);
+  if (b > 2048) b = 2048;
+  hipLaunchKernelGGL(vq_ema_accumulate_kernel, dim3((unsigned)b), dim3(256), 0, s, tokens, idx, n_tokens, n_global, n_codes, dim, amax,
+                     counts, counts + n_codes);
+  VQ_CHECK_LAUNCH("vq_vq_ema_accumulate");
+  return VQ_OK;
+}
+
+// sum over the block's 256 threads in a FIXED order (a tree over LDS: the same for every launch, block and rank)
+__device__ __forceinline__ double vq_ema_block_sum(double v, double* sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  sh[tid] = v;
+  __syncthreads();
+  for (int o = VQ_EMA_BLOCK / 2; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  return sh[0];
+}
+// pass 1, one thread per code: N_k <- g N_k + (1 - g) n_k — stored rounded to fp32, the unrounded value goes on to pass 2 in `nn_out` —
+// and the block's partial sums {sum N, sum n, sum n log n, codes with n > 0}
+__global__ __launch_bounds__(VQ_EMA_BLOCK) void vq_ema_sizes_kernel(const long long* __restrict__ counts, int n_codes, double decay,
+                                                                     float* __restrict__ cluster_size, double* __restrict__ nn_out,
+                                                                     double* __restrict__ part) {
+  __shared__ double sh[VQ_EMA_BLOCK];
+  const int k = blockIdx.x * VQ_EMA_BLOCK + threadIdx.x;
+  double nn = 0.0, n = 0.0;
+  if (k < n_codes) {
+    n = (double)counts[k];
+    nn = decay * (double)cluster_size[k] + (1.0 - decay) * n;
+    nn_out[k] = nn;
+    cluster_size[k] = (float)nn;
+  }
+  const double s0 = vq_ema_block_sum(nn, sh);
+  const double s1 = vq_ema_block_sum(n, sh);
+  const double s2 = vq_ema_block_sum(n > 0.0 ? n * log(n) : 0.0, sh);
+  const double s3 = vq_ema_block_sum(n > 0.0 ? 1.0 : 0.0, sh);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x * 4] = s0; part[blockIdx.x * 4 + 1] = s1; part[blockIdx.x * 4 + 2] = s2; part[blockIdx.x * 4 + 3] = s3;
+  }
+}
+// pass 2, one thread per codebook element: T = the partials summed in block order (every thread, the same order), then
+// m <- g m + (1 - g) s, the smoothed size (N + eps) / (T + K eps) * T and e = m / that — e from the unrounded m
+__global__ __launch_bounds__(VQ_EMA_BLOCK) void vq_ema_apply_kernel(const long long* __restrict__ sums, const double* __restrict__ nn_in,
+                                                                     const double* __restrict__ part, int n_parts, int n_codes, int dim,
+                                                                     int64_t n_global, const float* __restrict__ amax, double decay,
+                                                                     double eps, float* __restrict__ embed_sum,
+                                                                     float* __restrict__ codebook, float* __restrict__ usage) {
+  double T = 0.0, sn = 0.0, snl = 0.0, used = 0.0;
+  for (int b = 0; b < n_parts; ++b) { T += part[b * 4]; sn += part[b * 4 + 1]; snl += part[b * 4 + 2]; used += part[b * 4 + 3]; }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && usage) {
+    // perplexity = exp(-sum p log p), p = n / sum n:  -sum p log p = log(sum n) - (sum n log n) / sum n
+    usage[0] = sn > 0.0 ? (float)exp(log(sn) - snl / sn) : 0.f;
+    usage[1] = (float)used;
+  }
+  const double inv = 1.0 / vq_fixed_scale(*amax, n_global);
+  const double norm = T / (T + (double)n_codes * eps);
+  const int64_t total = (int64_t)n_codes * dim;
+  for (int64_t i = (int64_t)blockIdx.x * VQ_EMA_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * VQ_EMA_BLOCK) {
+    const int64_t k = i / dim;
+    const double m = decay * (double)embed_sum[i] + (1.0 - decay) * ((double)sums[i] * inv);
+    const double smoothed = (nn_in[k] + eps) * norm;
+    embed_sum[i] = (float)m;
+    codebook[i] = (float)(m / smoothed);
+  }
+}
+
+extern "C" int vq_vq_ema_update(void* workspace, size_t ws_bytes, int64_t n_global, const float* amax, int n_codes, int dim,
+                                double decay, double eps, float* cluster_size, float* embed_sum, float* codebook, float* usage,
+                                void* stream) {
+  VQ_REQUIRE(workspace && amax && cluster_size && embed_sum && codebook, VQ_ERR_INVALID, "vq_vq_ema_update: null pointer");
+  VQ_REQUIRE(n_codes > 0 && dim > 0 && n_global > 0, VQ_ERR_INVALID, "vq_vq_ema_update: empty problem (n_codes=%d dim=%d)", n_codes, dim);
+  VQ_REQUIRE(decay >= 0.0 && decay <= 1.0 && eps >= 0.0, VQ_ERR_INVALID, "vq_vq_ema_update: decay %g outside [0, 1] or eps %g < 0", decay, eps);
+  VQ_REQUIRE(ws_bytes >= vq_vq_ema_workspace(n_codes, dim), VQ_ERR_WORKSPACE, "vq_vq_ema_update: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const long long* counts = (const long long*)workspace;
+  const long long* sums = counts + n_codes;
+  double* nn = (double*)((char*)workspace + vq_ema_acc_bytes(n_codes, dim));
+  double* part = nn + n_codes;
+  const int nb = (int)vq_ceil_div(n_codes, VQ_EMA_BLOCK);
+  hipLaunchKernelGGL(vq_ema_sizes_kernel, dim3((unsigned)nb), dim3(VQ_EMA_BLOCK), 0, s, counts, n_codes, decay, cluster_size, nn, part);
+  VQ_CHECK_LAUNCH("vq_vq_ema_update(sizes)");
+  int64_t b2 = vq_ceil_div((int64_t)n_codes * dim, VQ_EMA_BLOCK);
+  if (b2 > 2048) b2 = 2048;
+  hipLaunchKernelGGL(vq_ema_apply_kernel, dim3((unsigned)b2), dim3(VQ_EMA_BLOCK), 0, s, sums, (const double*)nn, (const double*)part, nb,
+                     n_codes, dim, n_global, amax, decay, eps, embed_sum, codebook, usage);
+  VQ_CHECK_LAUNCH("vq_vq_ema_update(apply)");
+  return VQ_OK;
+}
+
+// Reseeding.  The hash (include/vqhip.h): g_k = splitmix64(splitmix64(seed + step) + k) mod n_global.
+__host__ __device__ __forceinline__ uint64_t vq_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// phase 0: candidate rows — cand[k] = the token the hash picks for code k if that code is dead (N_k < threshold) AND the token lives on
+// this rank ([token_offset, token_offset + n_local) of the global batch), zeros otherwise: summed over ranks, every dead row has
+// exactly one non-zero contributor.  (+ 0.f: a token's -0 becomes +0, as the sum over ranks would make it.)
+__global__ __launch_bounds__(256) void vq_ema_reseed_pick_kernel(const float* __restrict__ cluster_size, float threshold, uint64_t base,
+                                                                  const float* __restrict__ tok, int64_t n_local, int64_t token_offset,
+                                                                  int64_t n_global, int n_codes, int dim, float* __restrict__ cand) {
+  const int64_t total = (int64_t)n_codes * dim;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t k = i / dim;
+    const int d = (int)(i - k * dim);
+    float v = 0.f;
+    if (cluster_size[k] < threshold) {
+      const int64_t g = (int64_t)(vq_splitmix64(base + (uint64_t)k) % (uint64_t)n_global) - token_offset;
+      if (g >= 0 && g < n_local) v = tok[g * dim + d] + 0.f;
+    }
+    cand[i] = v;
+  }
+}
+// phase 1 (after the host's sum over ranks), one thread per codebook element: e_k = m_k = cand[k] for the dead codes, every other row is
+// left alone.  N is only READ here (every lane of a row needs the old value); the reset kernel below, one thread per code, follows
+// on the same stream and sets N_k = 1 for the same codes.
+__global__ __launch_bounds__(256) void vq_ema_reseed_install_kernel(const float* __restrict__ cluster_size, float threshold,
+                                                                     const float* __restrict__ cand, int n_codes, int dim,
+                                                                     float* __restrict__ embed_sum, float* __restrict__ codebook) {
+  const int64_t total = (int64_t)n_codes * dim;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (cluster_size[i / dim] < threshold) {
+      const float v = cand[i];
+      embed_sum[i] = v;
+      codebook[i] = v;
+    }
+  }
+}
+__global__ __launch_bounds__(256) void vq_ema_reseed_reset_kernel(float* __restrict__ cluster_size, float threshold, int n_codes) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k < n_codes && cluster_size[k] < threshold) cluster_size[k] = 1.f;
+}
+
+extern "C" int vq_vq_ema_reseed(int phase, float* cluster_size, float threshold, int64_t step, uint64_t seed, const float* tokens,
+                                int64_t n_local, int64_t token_offset, int64_t n_global, int n_codes, int dim, float* candidates,
+                                float* embed_sum, float* codebook, void* stream) {
+  VQ_REQUIRE(phase == 0 || phase == 1, VQ_ERR_INVALID, "vq_vq_ema_reseed: phase %d (0 = pick, 1 = install)", phase);
+  VQ_REQUIRE(cluster_size && candidates, VQ_ERR_INVALID, "vq_vq_ema_reseed: null pointer");
+  VQ_REQUIRE(n_codes > 0 && dim > 0, VQ_ERR_INVALID, "vq_vq_ema_reseed: empty problem (n_codes=%d dim=%d)", n_codes, dim);
+  hipStream_t s = (hipStream_t)stream;
+  if (phase == 0) {
+    VQ_REQUIRE(tokens, VQ_ERR_INVALID, "vq_vq_ema_reseed: null pointer (tokens)");
+    VQ_REQUIRE(n_local > 0 && token_offset >= 0 && n_global >= token_offset + n_local && step >= 0, VQ_ERR_INVALID,
+               "vq_vq_ema_reseed: tokens [%lld, %lld + %lld) outside the global batch of %lld, or step < 0", (long long)token_offset,
+               (long long)token_offset, (long long)n_local, (long long)n_global);
+    int64_t b = vq_ceil_div((int64_t)n_codes * dim, 256);
+    if (b > 2048) b = 2048;
+    const uint64_t base = vq_splitmix64(seed + (uint64_t)step);
+    hipLaunchKernelGGL(vq_ema_reseed_pick_kernel, dim3((unsigned)b), dim3(256), 0, s, (const float*)cluster_size, threshold, base, tokens,
+                       n_local, token_offset, n_global, n_codes, dim, candidates);
+    VQ_CHECK_LAUNCH("vq_vq_ema_reseed(pick)");
+    return VQ_OK;
+  }
+  VQ_REQUIRE(embed_sum && codebook, VQ_ERR_INVALID, "vq_vq_ema_reseed: null pointer (embed_sum / codebook)");
+  int64_t b1 = vq_ceil_div((int64_t)n_codes * dim, 256);
+  if (b1 > 2048) b1 = 2048;
+  hipLaunchKernelGGL(vq_ema_reseed_install_kernel, dim3((unsigned)b1), dim3(256), 0, s, (const float*)cluster_size, threshold,
+                     (const float*)candidates, n_codes, dim, embed_sum, codebook);
+  hipLaunchKernelGGL(vq_ema_reseed_reset_kernel, dim3((unsigned)vq_ceil_div(n_codes, 256)), dim3(256), 0, s, cluster_size, threshold,
+                     n_codes);
+  VQ_CHECK_LAUNCH("vq_vq_ema_reseed(install)");
+  return VQ_OK;
+}

@@ -224,7 +224,10 @@ class VAETrainStep:
         self.do_clamp, self.clamp_th = do_clamp, clamp_th
         self.max_steps, self.warmup_steps = max_steps, warmup_steps
         named = list(vae.named_parameters())
-        if quantizer is not None:                 # the codebook trains with the VAE's main group, its gradient rides in the VAE buckets
+        self._ema_vq = quantizer is not None and getattr(quantizer, "ema", False)
+        # an EMA codebook has no optimizer: not in optimizer_G (no AdamW, no weight decay), not in the gradient buckets; its update is
+        # applied where optimizer_G steps (quantizer.ema_update)
+        if quantizer is not None and not self._ema_vq:   # the codebook trains with the VAE's main group, its gradient rides in the VAE buckets
             # ... at the place its gradient becomes final in a backward pass: after the whole decoder, before the encoder.  Buckets are
             # cut in reverse parameter order and go on the wire strictly in index order (BucketedGradReducer): appended LAST, the
             # codebook would share bucket 0 with the decoder's last layers and hold every decoder bucket back until the decoder's
@@ -396,6 +399,8 @@ class VAETrainStep:
         LeCam anchors, the random streams the step draws from — so that `state_restore` puts the run back exactly here (bench.py:
         the rehearsal that measures the loss scales the timed steps need)."""
         return {"G": self.optimizer_G.snapshot(moments=True),
+                # an EMA codebook (with its cluster sizes, sums and first-forward flag) is no part of optimizer_G's flat buffers
+                "vq_ema": self.quantizer.ema_state() if self._ema_vq else None,
                 "D": self.optimizer_D.snapshot(moments=True) if self.optimizer_D is not None else None,
                 "global_step": self.global_step, "lecam": self.lecam_anchor.clone(),
                 "py_rng": self.rng.getstate() if (self.rng and hasattr(self.rng, "getstate")) else None,
@@ -404,6 +409,8 @@ class VAETrainStep:
 
     def state_restore(self, snap: dict) -> None:
         self.optimizer_G.restore(snap["G"])
+        if self._ema_vq and snap.get("vq_ema") is not None:
+            self.quantizer.ema_restore(snap["vq_ema"])
         if self.optimizer_D is not None and snap["D"] is not None:
             self.optimizer_D.restore(snap["D"])
         self.global_step = snap["global_step"]
@@ -537,6 +544,8 @@ class VAETrainStep:
                 z_look = z_look.wait()
                 if self.do_clamp:
                     z_look = z_look.clamp(-self.clamp_th, self.clamp_th)
+            if self._ema_vq:
+                self.quantizer.frozen = self._dry          # a calibration pass leaves no statistics and initialises nothing
             z_s, vq_loss, indices = self.quantizer(z, lookup_from=z_look) if z_look is not None else self.quantizer(z)
             out["indices"] = indices
         else:
@@ -634,6 +643,10 @@ class VAETrainStep:
             self._sync_window(self.reducer_G)
             self.optimizer_G.step()                        # :702 (dropped on the device if a binary16 gradient was clipped)
             self._close_window(0)
+            if self._ema_vq:                               # the codebook's step: EMA update (+ reseeding on its cadence), no host sync
+                usage = self.quantizer.ema_update()
+                if usage is not None:
+                    out["vq_perplexity"], out["vq_codes_used"] = usage[0], usage[1]
         self.optimizer_G.zero_grad()                       # :703
         if not self._dry:
             self.global_step += 1                          # lr_scheduler.step() (:704) == recompute next call
@@ -686,7 +699,9 @@ def load_checkpoint(vae: VAE, path: str, quantizer=None) -> None:
     """--load_path (vae_trainer.py:505-513): a torch.save'd state dict (any of the prefixes) or a safetensors export.
     The fp32 master weights are overwritten in place (bf16 files are widened), strict=True like the reference.
     `quantizer.*` keys (save_checkpoint with a VectorQuantizer) go to `quantizer` when one is given — strict as well: a
-    codebook checkpoint must match the configured codebook — and are dropped otherwise."""
+    codebook checkpoint must match the configured codebook — and are dropped otherwise.  An EMA quantizer's cluster sizes and
+    sums ride under the same prefix; loading a file without them into an EMA quantizer starts them from the loaded codebook
+    (sizes 1, sums = codebook) and says so in the log (VectorQuantizer._load_from_state_dict)."""
     with open(path, "rb") as f:
         head = f.read(8)
     is_zip_or_pickle = head[:2] == b"PK" or head[:1] == b"\x80"
@@ -979,6 +994,8 @@ def logged_scalars(res: dict, step: VAETrainStep, do_ganloss: bool) -> dict:
     rec["z_quantiles/qs"] = qs
     if "vq_loss" in res:
         rec["vq_loss"] = float(res["vq_loss"])
+    if "vq_perplexity" in res:                # EMA codebook: usage of the step's batch (quantizer.ema_update)
+        rec["vq_perplexity"], rec["vq_codes_used"] = float(res["vq_perplexity"]), float(res["vq_codes_used"])
     if do_ganloss:
         st = res["disc_stats"].tolist()       # {loss_real, loss_fake, mean_real, mean_fake, n_correct, count}
         anchor = step.lecam_anchor.tolist()
