@@ -124,7 +124,10 @@ typedef struct VqGnBwdFuse {
  *                    the short-M rule (<= one 64x128 block per CU) picks 64-pixel ones; +(40 << 4) = the one-tap 32-row tile where the
  *                    nine-tap kernel would serve a layer of <= 32 output channels (hint 5 forces that one at any size);
  *                    +(48 << 4) = the generic tile kernels where the persistent patch-conv data-gradient kernel would run,
- *                    +(56 << 4) = that kernel at any size.
+ *                    +(56 << 4) = that kernel at any size;
+ *                    +(80 << 4) = the nine-tap 128-channel x 256-pixel tile (one 16 x 16 patch, 64c x 128p waves, VQ_BF16 / VQ_F16)
+ *                    wherever the shape admits it (a nine-tap shape with Ho % 16 == 0; with hint 5 at any size), +(88 << 4) = the
+ *                    nine-tap 128 x 128 tile where that one would run.
  *   vq_conv2d_wgrad: 64 / 128 / 256 = that one-tap LDS-DMA tile, +4 = never the three-tap kernel, +1 = the 4 B/lane split
  *                    reduction, +16 = the three-tap kernel with unstaggered staging; bits 16-31 = forced split-K count (0 = planned).
  * Any other value selects a compile-time ablation / pricing knob that exists only in `make ABLATE=1` builds: a release library

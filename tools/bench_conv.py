@@ -19,6 +19,7 @@ SHAPES = [  # Cin, Cout, H(out), R, stride, up
     (128, 256, 128, 3, 1, 1), (256, 128, 256, 1, 1, 1), (128, 8, 256, 3, 1, 1), (8, 128, 256, 3, 1, 1),
     (64, 64, 256, 3, 1, 1), (512, 512, 16, 3, 1, 1), (512, 512, 8, 3, 1, 1), (8, 64, 256, 3, 1, 1),
     (64, 64, 512, 3, 1, 1), (128, 64, 512, 3, 1, 1),      # 16, 17: the HR decoder's last level of the reference's launch line (l1)
+    (128, 128, 128, 3, 1, 1),                             # 18: the 128-channel level at 128 x 128
 ]
 
 def timeit(fn, iters=int(os.environ.get("VQ_ITERS", "20"))):

@@ -153,7 +153,7 @@ template <> struct XRegs<VQ_F16, 1> { vq_u4 q; };
 template <> struct XRegs<VQ_F16X2, 1> { vq_u4 q; };
 template <int SPLIT> struct XRegs<VQ_F32, SPLIT> { vq_f4 a, b; };
 
-template <int DT, int BC, int BP, int WC, int WP, int PERM = 0, int MAXU = 4>
+template <int DT, int BC, int BP, int WC, int WP, int PERM = 0, int MAXU = 4, int GN2 = 0>
 __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds, f32x16 (&acc)[WC / 32][WP / 32], int c0, int p0,
                                                int wc0, int wp0, float alpha_in = -0.f, int mbase_in = -1);   // defined with the LDS-DMA kernels below
 template <int BC, int BP, int WC, int WP, int PERM = 0>
@@ -462,7 +462,10 @@ __device__ __attribute__((aligned(128))) unsigned int g_vq_zero_page[64];
 // output move in fully coalesced 16 B/lane accesses.  (With a residual the sum is rounded twice, bf16(bf16(acc +
 // bias) + res): one extra bf16 ulp at most, throughput mode only — the parity mode runs conv_igemm_kernel.)
 // Precondition: every wave of the block is past the last barrier of the main loop (the tiles in `lds` are dead).
-template <int DT, int BC, int BP, int WC, int WP, int PERM, int MAXU>
+// GN2 (the 16 x 16-patch nine-tap tile): the GroupNorm partials leave as the rows of the two 8 x 16 patches the tile is made of — a
+// thread's first ITEMS / 2 items are the upper patch, the rest the lower one, each half with its own pivot — so that the partial
+// buffer, and with it the statistics bit for bit, are those of the 128-pixel tile (p.gn_bp = 128, p.gn_tiles = 128-pixel tiles).
+template <int DT, int BC, int BP, int WC, int WP, int PERM, int MAXU, int GN2>
 __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds, f32x16 (&acc)[WC / 32][WP / 32], int c0, int p0,
                                                int wc0, int wp0, float alpha_in, int mbase_in) {
   constexpr int FC = WC / 32, FP = WP / 32, NW = (BC / WC) * (BP / WP);
@@ -626,6 +629,8 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds
   // GroupNorm partials of this thread's slot, channels 0-3 | 4-7: (sum, sum of squares) of v - pivot, the pivot being the first value of
   // the lane that starts the group in this wave (gn_silu.hip's header: shifted moments, never E[x^2] - E[x]^2 of raw fp32 sums)
   float gsum[4] = {0.f, 0.f, 0.f, 0.f}, gpiv[2] = {0.f, 0.f};
+  float gsum2[4] = {0.f, 0.f, 0.f, 0.f}, gpiv2[2] = {0.f, 0.f};     // (GN2: the lower half's)
+  static_assert(!GN2 || (ITEMS % (2 * U) == 0 && PSTEP == 16), "GN2: a round lies in one half; an item is one patch row");
   float fuse_c[16];                                // (pricing knob 6 only: per-channel sums of the fused GroupNorm backward)
 #pragma unroll
   for (int e = 0; e < 16; ++e) fuse_c[e] = 0.f;
@@ -728,6 +733,11 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds
         gpiv[0] = __shfl(v[0][0], src);
         gpiv[1] = p.gn_cg == 4 ? __shfl(v[0][4], src) : gpiv[0];
       }
+      if (GN2 && p.gn_part && r * U == ITEMS / 2 && u == 0) {
+        const int spg = p.gn_cg >= 8 ? p.gn_cg >> 3 : 1, src = (lane % SPRW) & ~(spg - 1);
+        gpiv2[0] = __shfl(v[0][0], src);
+        gpiv2[1] = p.gn_cg == 4 ? __shfl(v[0][4], src) : gpiv2[0];
+      }
       if (live[r & 1][u]) {
         // streaming store: the output is not touched again by this kernel, and written through L2 in the ordinary way it evicted
         // the weight / halo lines the main loop keeps re-reading (measured: +13 % / +8 % on 128 ch @256^2, +2.5 % on the 256 tile)
@@ -739,7 +749,12 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds
           if (count_range) rng_pk = vq_pkmax16(vq_pkmax16(rng_pk, q.x & 0x7fff7fffu, q.y & 0x7fff7fffu), q.z & 0x7fff7fffu, q.w & 0x7fff7fffu);
           vq_store16_nt((vq_f16*)p.y + off[r & 1][u], q);
         } else St::store8_nt(p.y, off[r & 1][u], v[u]);
-        if (p.gn_part) {
+        if (GN2 && p.gn_part && r * U >= ITEMS / 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { const float dv = v[u][e] - gpiv2[0]; gsum2[0] += dv; gsum2[1] += dv * dv; }
+#pragma unroll
+          for (int e = 4; e < 8; ++e) { const float dv = v[u][e] - gpiv2[1]; gsum2[2] += dv; gsum2[3] += dv * dv; }
+        } else if (p.gn_part) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { const float dv = v[u][e] - gpiv[0]; gsum[0] += dv; gsum[1] += dv * dv; }
 #pragma unroll
@@ -786,26 +801,41 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds
     for (int m = SPRW; m < 64; m <<= 1) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) gsum[e] += __shfl_xor(gsum[e], m);
+      if constexpr (GN2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gsum2[e] += __shfl_xor(gsum2[e], m);
+      }
     }
     const int cg = p.gn_cg, wave = tid >> 6;
     const int tile_lin = p0 / BP;                  // pixel tile index over the whole batch (patch tiles and linear tiles alike)
-    const int n = tile_lin / p.gn_tiles, tile = tile_lin - n * p.gn_tiles;
-    float* row = p.gn_part + (((int64_t)n * p.gn_tiles + tile) * NW + wave) * p.gn_G * 2;
-    // the row leaves as (mean, M2 = sum (v - mean)^2) per group; BP / NW pixels x cg channels each (a power of two: exact reciprocal).
+    // the row leaves as (mean, M2 = sum (v - mean)^2) per group; RP pixels x cg channels each (a power of two: exact reciprocal).
     // The writing lane is the one whose first value was the pivot.
-    const float icnt = 1.f / (float)((BP / NW) * cg);
-    if (cg == 4) {
-      const int g = (c0 + sl * 8) >> 2;
-      if (lane < SPRW && g < p.gn_G) {
-        row[g * 2] = gpiv[0] + gsum[0] * icnt; row[g * 2 + 1] = gsum[1] - gsum[0] * (gsum[0] * icnt);
-        if (g + 1 < p.gn_G) { row[g * 2 + 2] = gpiv[1] + gsum[2] * icnt; row[g * 2 + 3] = gsum[3] - gsum[2] * (gsum[2] * icnt); }
+    constexpr int RP = (GN2 ? BP / 2 : BP) / NW;
+    const float icnt = 1.f / (float)(RP * cg);
+    auto write_row = [&](float* row, const float (&gs)[4], const float (&gp)[2]) {
+      if (cg == 4) {
+        const int g = (c0 + sl * 8) >> 2;
+        if (lane < SPRW && g < p.gn_G) {
+          row[g * 2] = gp[0] + gs[0] * icnt; row[g * 2 + 1] = gs[1] - gs[0] * (gs[0] * icnt);
+          if (g + 1 < p.gn_G) { row[g * 2 + 2] = gp[1] + gs[2] * icnt; row[g * 2 + 3] = gs[3] - gs[2] * (gs[2] * icnt); }
+        }
+      } else {
+        float a = gs[0] + gs[2], b = gs[1] + gs[3];
+        const int spg = cg >> 3;                   // slots per group: 1, 2 or 4
+        for (int m = 1; m < spg; m <<= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
+        const int g = (c0 + sl * 8) / cg;
+        if (lane < SPRW && (sl & (spg - 1)) == 0 && g < p.gn_G) { row[g * 2] = gp[0] + a * icnt; row[g * 2 + 1] = b - a * (a * icnt); }
       }
+    };
+    if constexpr (GN2) {
+      // this 16 x 16 patch (ty, tx) = the 8 x 16 patches (2 ty, tx) and (2 ty + 1, tx) of the 128-pixel tiling (p.gn_tiles per image)
+      const int tpi = p.gn_tiles >> 1, n = tile_lin / tpi, t = tile_lin - n * tpi, ty = t / p.pt_tx, tx = t - ty * p.pt_tx;
+      float* row = p.gn_part + (((int64_t)n * p.gn_tiles + 2 * ty * p.pt_tx + tx) * NW + wave) * p.gn_G * 2;
+      write_row(row, gsum, gpiv);
+      write_row(row + (int64_t)p.pt_tx * NW * p.gn_G * 2, gsum2, gpiv2);
     } else {
-      float a = gsum[0] + gsum[2], b = gsum[1] + gsum[3];
-      const int spg = cg >> 3;                     // slots per group: 1, 2 or 4
-      for (int m = 1; m < spg; m <<= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-      const int g = (c0 + sl * 8) / cg;
-      if (lane < SPRW && (sl & (spg - 1)) == 0 && g < p.gn_G) { row[g * 2] = gpiv[0] + a * icnt; row[g * 2 + 1] = b - a * (a * icnt); }
+      const int n = tile_lin / p.gn_tiles, tile = tile_lin - n * p.gn_tiles;
+      write_row(p.gn_part + (((int64_t)n * p.gn_tiles + tile) * NW + wave) * p.gn_G * 2, gsum, gpiv);
     }
   }
 }
@@ -1450,6 +1480,12 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap3
 //   (Hiding the WEIGHT loads instead was tried first and is unsafe under this kernel's register pressure: hipcc treats an asm
 //   load's destination as written at once and moved an address through it — memory faults at full size, r2 notes.)
 // WA bit 1: fragment addresses in registers, 32-KiB buffer stride, conflict-free lane -> pixel map (tap9_perm).
+// WA bit 2 (with bits 0-1: WA = 7): ONE halo buffer, for the 128-channel x 256-pixel tile (16 x 16 patch, 2 x 2 waves of 64c x 128p:
+//   8 MFMAs per 2 KiB of weight fragments instead of 4).  Two 41-KiB halo buffers beside a 64-KiB epilogue slab would leave one block
+//   per CU; with one buffer the block is 64 KiB and two fit.  The next chunk's DMA is issued after a barrier at the chunk's end and
+//   awaited at once — the co-resident block's k-loop covers it.  K order unchanged: bit-identical to the 128 x 128 tile.  128
+//   accumulators leave ~100 registers for everything else: the pieces' source offsets wait in the LDS behind the halo tile, fragment
+//   b + 2 shares fragment b's address registers, weight addresses are scalar base + 32-bit offset.  228 VGPRs, no scratch.
 // (A three-blocks-per-CU form — adjacent buffers, 32-bit piece offsets, 168 VGPRs — was measured neutral in round 2 and removed:
 //   profiles/r2x_tap9_three_blocks_*; it last existed in commit 2da2460.)
 // (Round 6: TWO taps of weight fragments in flight — a register ring of 8 k-steps, slot block = tap & 1, the two blocks changing hands
@@ -1467,9 +1503,10 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   constexpr int PPW = (PMAX + NW - 1) / NW;            // pieces per wave
   constexpr int XT = PMAX * 8 * BK;                    // elements per buffer
   // WA = 3: second buffer at a power-of-two distance, so that (buffer, k-step) enter a fragment address by ONE xor
-  constexpr bool ASMDMA = (WA & 1) != 0, REGADDR = (WA & 2) != 0;
-  static_assert((WA & ~3) == 0, "WA: bit 0 = asm tile DMA, bit 1 = register fragment addresses");
-  constexpr int XTS = REGADDR ? 16384 : XT;            // buffer stride in elements (32 KiB for the one-xor form)
+  constexpr bool ASMDMA = (WA & 1) != 0, REGADDR = (WA & 2) != 0, ONEBUF = (WA & 4) != 0;
+  static_assert((WA & ~7) == 0, "WA: bit 0 = asm tile DMA, bit 1 = register fragment addresses, bit 2 = one halo buffer");
+  static_assert(!ONEBUF || WA == 7, "the one-buffer form is built on the asm DMA and the register addresses");
+  constexpr int XTS = (REGADDR && !ONEBUF) ? 16384 : XT;   // buffer stride in elements (32 KiB for the one-xor form)
   static_assert(PPW <= 36, "one DMA piece per (tap, k-step)");
   static_assert(!REGADDR || XT <= XTS, "halo tile larger than the 32-KiB buffer stride");
 
@@ -1508,8 +1545,15 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   // ---- halo slots owned by this lane: piece (wave + NW * i), row lr of the piece, physical 16-byte slot lp -------
   const int lr = lane >> 3, lp = lane & 7;
   const int cpt = p.d.Cin >> 6;
-  const vq_bf16* pa[PPW];
-  int inca[PPW];
+  // ONEBUF: one 32-bit element offset per piece (negative = zero page; the launcher checks that the input has < 2^31 elements), kept in
+  // the LDS behind the halo tile (the epilogue's slab is larger than the tile) and read back once per chunk: 128 accumulators leave
+  // no room for three registers per piece.  Chunk 0 is issued as the offsets are formed.
+  const vq_bf16* pa[ONEBUF ? 1 : PPW];
+  int inca[ONEBUF ? 1 : PPW];
+  int* const xo_lds = (int*)(lds + XT) + tid;          // [PPW][NW * 64]
+  // (the wave index as a scalar: the pieces' LDS destinations stay out of the vector registers)
+  const int wave_u = ONEBUF ? __builtin_amdgcn_readfirstlane(wave) : wave;
+  static_assert(!ONEBUF || (size_t)XT * 2 + (size_t)PPW * NW * 64 * 4 <= (size_t)BP * BC * 2, "piece offsets behind the halo tile");
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
     const int slot = (wave + NW * i) * 8 + lr;
@@ -1517,11 +1561,30 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
     const int hy = slot / HWD, hx = slot - hy * HWD;
     const int iy = ty0 - 1 + hy, ix = tx0 - 1 + hx;
     const int ok = (int)(slot < NSLOT) & (int)((unsigned)ix < (unsigned)Wv) & (int)((unsigned)iy < (unsigned)Hv);
-    const int64_t off = (int64_t)((pn * p.d.H + (iy >> p.ush)) * p.d.W + (ix >> p.ush)) * p.d.Cin + lsa;
-    const uintptr_t a_ok = (uintptr_t)(xbase + off), a_zero = (uintptr_t)(zero + lsa);
-    pa[i] = (const vq_bf16*)(ok ? a_ok : a_zero);
-    inca[i] = ok ? BK : 0;
+    if constexpr (ONEBUF) {
+      if (NW * i + NW <= PMAX || wave_u + NW * i < PMAX) {      // (first part: compile-time)
+        const int xo = ok ? ((pn * p.d.H + (iy >> p.ush)) * p.d.W + (ix >> p.ush)) * p.d.Cin + lsa : ~lsa;   // (< 0: zero page + lsa)
+        xo_lds[i * NW * 64] = xo;
+        glds16_asm(xo >= 0 ? xbase + xo : zero + lsa, lds + (wave_u + NW * i) * 8 * BK);
+      }
+    } else {
+      const int64_t off = (int64_t)((pn * p.d.H + (iy >> p.ush)) * p.d.W + (ix >> p.ush)) * p.d.Cin + lsa;
+      const uintptr_t a_ok = (uintptr_t)(xbase + off), a_zero = (uintptr_t)(zero + lsa);
+      pa[i] = (const vq_bf16*)(ok ? a_ok : a_zero);
+      inca[i] = ok ? BK : 0;
+    }
   }
+  auto stage_chunk = [&](int cc) {                     // ONEBUF: the whole halo tile of chunk cc >= 1 into the one buffer
+    int xo[PPW];
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) xo[i] = (NW * i + NW <= PMAX || wave_u + NW * i < PMAX) ? xo_lds[i * NW * 64] : -1;
+#pragma unroll
+    for (int i = 0; i < PPW; ++i)
+      if (NW * i + NW <= PMAX || wave_u + NW * i < PMAX) {      // (first part: compile-time)
+        const vq_bf16* src = xo[i] >= 0 ? xbase + (int64_t)xo[i] + cc * BK : zero + ~xo[i];
+        glds16_asm(src, lds + (wave_u + NW * i) * 8 * BK);
+      }
+  };
   auto stage_piece = [&](int buf, int i) {             // i compile-time after unrolling
     if (wave + NW * i < PMAX) {
       if constexpr (ASMDMA) glds16_asm(pa[i], lds + buf * XTS + (wave + NW * i) * 8 * BK);
@@ -1550,19 +1613,42 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   // REGADDR: byte address of (tap, fragment b) at k-step 0 in buffer 0, kept in registers: 9 * FP VGPRs instead of ~7 VALU
   // operations per read.  The slot index of k-step kk is ((2 kk) | fh) ^ key = (2 kk) ^ (fh ^ key) (2 kk has no bit 0), i.e.
   // byte bits 5-6, and the second buffer is 2^15 bytes away: address = abase ^ ((kk << 5) | (buf << 15)).
-  unsigned abase[REGADDR ? 9 : 1][FP];
+  // ONEBUF (FP = 4): fragment b + 2 lies four patch rows = 72 halo rows below fragment b — its key (row >> 1) & 7 differs by 36 = 4
+  // (mod 8), one more xor of byte bit 6, and the 72 rows are the read's immediate offset: 18 address registers instead of 36.
+  constexpr int FPA = ONEBUF ? 2 : FP;
+  static_assert(!ONEBUF || (FP == 4 && WP == 128 && TW == 16), "fragment b + 2 = fragment b + 72 halo rows");
+  unsigned abase[REGADDR ? 9 : 1][FPA];
   if constexpr (REGADDR) {
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-      for (int b = 0; b < FP; ++b) {
+      for (int b = 0; b < FPA; ++b) {
         const int row = rowb[b] + (tap / 3) * HWD + (tap % 3);
         abase[tap][b] = (unsigned)(row * BK * 2 + ((frag_slot<X2>(0, fh) ^ ((row >> 1) & 7)) << 4));
       }
   }
+  unsigned tadr[2][4];                                 // (ONEBUF: the current tap's addresses)
   auto frag_load = [&](int buf, int tap, int kk, int slot) {
     if constexpr (REGADDR) {
       const unsigned x = frag_xor<X2>(kk) | (unsigned)(buf << 15);
+      if constexpr (ONEBUF) {
+        // the tap's eight addresses (2 fragments x 4 k-steps; fragments b + 2 read them in the order k ^ 2) are formed at its first
+        // k-step from an OPAQUE copy of the base: left to itself hipcc keeps the xor-ed addresses of all nine taps of the chunk loop
+        // in registers — 186 spilled VGPRs, and a vmcnt(0) in front of every reload
+        if (kk == 0) {
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            unsigned ab = abase[tap][b];
+            VQ_OPAQUE_VGPR(ab);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tadr[b][q] = ab ^ frag_xor<X2>(q);
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < FP; ++b)
+          bfr[slot][b] = *(const s16x8*)((const char*)lds + tadr[b & 1][b >= 2 ? (kk ^ 2) : kk] + (b >= 2 ? 4 * HWD * BK * 2 : 0));
+        return;
+      }
 #pragma unroll
       for (int b = 0; b < FP; ++b) bfr[slot][b] = *(const s16x8*)((const char*)lds + (abase[tap][b] ^ x));
       return;
@@ -1581,6 +1667,7 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   // ---- weight fragments (fragment-order packed layout, see pack_weight_kernel layout 1) --------------------------
   s16x8 wf[BK / 16][FC];
   const vq_bf16* wrow[FC];
+  unsigned woff[FC];
   {
     const int ncb = (p.d.Cout + 31) >> 5;
 #pragma unroll
@@ -1588,14 +1675,26 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
       int cb = ((c0 + wc0) >> 5) + a;
       if (cb >= ncb) cb = ncb - 1;
       wrow[a] = p.w + ((int64_t)cb * (p.Kp >> 4)) * 512 + lane * 8;
+      woff[a] = (unsigned)(cb * (p.Kp >> 4)) * 1024u + (unsigned)lane * 16u;
     }
   }
   auto kb_of = [&](int tap, int cc) -> int { return ((tap * p.d.Cin) >> 4) + cc * (BK / 16); };
+  // ONEBUF: the lane's part of a weight address as a 32-bit byte offset (the launcher checks the packed weights' size) beside a
+  // scalar base — two registers instead of four, and no 64-bit vector adds per request
+  auto wload = [&](int a, int kb) -> s16x8 {
+    if constexpr (ONEBUF) {
+      unsigned o = woff[a];
+      VQ_OPAQUE_VGPR(o);                               // (the zero-extension stays beside the load: scalar base + 32-bit offset form)
+      return *(const s16x8*)((const char*)p.w + (int64_t)kb * 1024 + o);
+    }
+    else return *(const s16x8*)(wrow[a] + (int64_t)kb * 512);
+  };
 #pragma unroll
   for (int kk = 0; kk < BK / 16; ++kk)
 #pragma unroll
-    for (int a = 0; a < FC; ++a) wf[kk][a] = *(const s16x8*)(wrow[a] + (int64_t)(kb_of(0, 0) + kk) * 512);
+    for (int a = 0; a < FC; ++a) wf[kk][a] = wload(a, kb_of(0, 0) + kk);
 
+  if constexpr (!ONEBUF)
 #pragma unroll
   for (int i = 0; i < PPW; ++i) stage_piece(0, i);
   wait_vmcnt<0>();
@@ -1603,7 +1702,7 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   VQ_STAMP(11);
   raw_barrier();
   for (int cc = 0; cc < cpt; ++cc) {
-    const int buf = cc & 1;
+    const int buf = ONEBUF ? 0 : (cc & 1);
     const bool more_x = cc + 1 < cpt;
     frag_load(buf, 0, 0, 0);
 #pragma unroll
@@ -1623,7 +1722,7 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
         }
       vq_sched_fence();
       const int rk = X2 ? (kk ^ 1) : kk;             // the weight register whose last use this step was
-      if (v < PPW && more_x) stage_piece(buf ^ 1, v);  // next chunk's DMA, one piece per step
+      if constexpr (!ONEBUF) { if (v < PPW && more_x) stage_piece(buf ^ 1, v); }  // next chunk's DMA, one piece per step
       // refill the weight registers of this k-step for the next (tap, chunk)
       int ntap = tap + 1, ncc = cc;
       if (ntap == 9) { ntap = 0; ++ncc; }
@@ -1632,12 +1731,17 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
         // condition makes hipcc assume the worst at every later wait — the last k-steps of every chunk drained the queue
         if (ncc >= cpt) ncc = 0;
 #pragma unroll
-        for (int a = 0; a < FC; ++a) wf[rk][a] = *(const s16x8*)(wrow[a] + (int64_t)(kb_of(ntap, ncc) + rk) * 512);
+        for (int a = 0; a < FC; ++a) wf[rk][a] = wload(a, kb_of(ntap, ncc) + rk);
       } else if (ncc < cpt) {
 #pragma unroll
-        for (int a = 0; a < FC; ++a) wf[rk][a] = *(const s16x8*)(wrow[a] + (int64_t)(kb_of(ntap, ncc) + rk) * 512);
+        for (int a = 0; a < FC; ++a) wf[rk][a] = wload(a, kb_of(ntap, ncc) + rk);
       }
     }
+    // ONEBUF: the next chunk lands in the buffer this one was read from — once every wave's last fragment read has returned (they
+    // have: the chunk's last MFMAs were issued with them), and awaited at once; the co-resident block's k-loop covers the wait
+    if constexpr (ONEBUF) {
+      if (more_x) { raw_barrier(); stage_chunk(cc + 1); wait_vmcnt<0>(); }
+    } else
     // every DMA piece of this chunk is older than the weight requests of its last four k-steps, which may stay in flight
     if constexpr (ASMDMA) wait_vmcnt<4 * FC>();
     else { if (more_x) wait_vmcnt<FC>(); else wait_vmcnt<0>(); }
@@ -1646,7 +1750,7 @@ __global__ __launch_bounds__((BC / WC) * (BP / WP) * 64, 2) void conv_igemm_tap9
   VQ_STAMP(12);
   // (all 8 items of a thread in ONE round — MAXU = 8 — was measured: +-0, profiles/r3k_*)
   if constexpr (X2) igemm_epilogue_x2<BC, BP, WC, WP, REGADDR>(p, lds, acc, c0, p0, wc0, wp0, alpha_s, (pn * p.d.Ho + ty0) * p.d.Wo + tx0);
-  else igemm_epilogue<DT, BC, BP, WC, WP, REGADDR>(p, lds, acc, c0, p0, wc0, wp0, alpha_s, (pn * p.d.Ho + ty0) * p.d.Wo + tx0);
+  else igemm_epilogue<DT, BC, BP, WC, WP, REGADDR, 4, ONEBUF>(p, lds, acc, c0, p0, wc0, wp0, alpha_s, (pn * p.d.Ho + ty0) * p.d.Wo + tx0);
   VQ_STAMP(13);
 }
 
@@ -2392,7 +2496,8 @@ static int launch_glds(ConvParams& p, hipStream_t stream) {
 //   bits 0-2 (tile): 1 = the 128x128 tiles, 2 = 32x128 tiles, 3 = the 256x256 tile, 5 = nine-tap kernel wherever the shape allows,
 //                    6 = no three-tap / nine-tap kernel, 7 = three-tap kernel wherever eligible;  bit 3 (+8) = weights through LDS
 //   bits 4.. (dbg):  512 = the one-tap 256x256 tile where the patch-staged one would run, 16 = 128-pixel tiles where the short-M
-//                    rule picks 64-pixel ones;  everything else selects compile-time ablations / epilogue pricing knobs that
+//                    rule picks 64-pixel ones, 80 = the nine-tap 128 x 256 tile (64c x 128p waves) wherever the shape admits it,
+//                    88 = the nine-tap 128 x 128 tile where that one would run;  everything else selects compile-time ablations / epilogue pricing knobs that
 //                    exist only in `make ABLATE=1` builds: a release library refuses those values with VQ_ERR_UNSUPPORTED.
 //                    (The measured-and-not-adopted KERNELS of rounds 2-3 — 128-row and 128 x 512 patch tiles, the resident-weight
 //                    64-channel kernel; dbg 1024 / 2048 / 4096 / 24 / 8200-8203 — were removed in round 5: they last existed in
@@ -2405,7 +2510,7 @@ static bool hint_supported(const VqConvDesc* d) {
   (void)t;
   return !(g == 1024 || g == 2048 || g == 4096 || g == 24 || (g >= 8200 && g <= 8203));      // the removed kernels' hints
 #else
-  return t != 4 && (g == 0 || g == 512 || g == 16 || g == 40 || g == 48 || g == 56 || g == 72);
+  return t != 4 && (g == 0 || g == 512 || g == 16 || g == 40 || g == 48 || g == 56 || g == 72 || g == 80 || g == 88);
 #endif
 }
 
@@ -2470,10 +2575,19 @@ static int launch_tap3(ConvParams& p, hipStream_t stream) {
 }
 template <int DT, int BC, int BP, int WC, int WP, int WA = 0>
 static int launch_tap9(ConvParams& p, hipStream_t stream) {
-  if (p.gn_part && (p.gn_bp != BP || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
+  // (WA & 4: the 256-pixel tile writes the partial rows of its two 128-pixel halves, igemm_epilogue GN2)
+  if (p.gn_part && (p.gn_bp != ((WA & 4) ? BP / 2 : BP) || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
   constexpr int NW = (BC / WC) * (BP / WP);
   constexpr int PMAX = ((BP / 16 + 2) * 18 + 7) / 8;
-  constexpr size_t LDS_BYTES = ((WA & 2) ? (size_t)32768 : (size_t)PMAX * 8 * 64 * sizeof(vq_bf16)) + (size_t)PMAX * 8 * 64 * sizeof(vq_bf16);
+  constexpr size_t HALO_BYTES = (size_t)PMAX * 8 * 64 * sizeof(vq_bf16), EPI_BYTES = (size_t)BP * BC * sizeof(vq_bf16);
+  // (WA & 4: one halo buffer, or the epilogue's slab where that is larger)
+  constexpr size_t LDS_BYTES = (WA & 4) ? (HALO_BYTES > EPI_BYTES ? HALO_BYTES : EPI_BYTES)
+                                        : ((WA & 2) ? (size_t)32768 : HALO_BYTES) + HALO_BYTES;
+  static_assert(!(WA & 4) || (DT != VQ_F16X2 && 2 * LDS_BYTES <= 160 * 1024), "the one-buffer form: two blocks per CU, no fp32 epilogue slab");
+  if ((WA & 4) && ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin >= ((int64_t)1 << 31) || (int64_t)vq_round_up(p.d.Cout, 32) * p.Kp >= ((int64_t)1 << 31))) {
+    vq_set_error("vq_conv2d_fwd(tap9): input or packed weights of 2^31 elements or more");
+    return VQ_ERR_UNSUPPORTED;
+  }
   static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16), "the epilogue transposes the output tile through the same LDS");
   static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
   p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
@@ -2488,7 +2602,7 @@ static int launch_tap9(ConvParams& p, hipStream_t stream) {
   // must land first and an epilogue — and more resident blocks are what covers those two ends: forward +10-18 %, data gradient +5-8 %
   // (profiles/r6e_c64_onebuf_ab.txt; a deeper weight-fragment ring instead: +-1 %, r6f_tap9_wd_ab.txt).
   size_t lds_bytes = LDS_BYTES;
-  if (DT != VQ_F16X2 && p.d.Cin == 64 && hint_dbg(&p.d) != 72) {      // (the VQ_F16X2 epilogue's fp32 slab is larger; dbg 72 = A/B)
+  if (DT != VQ_F16X2 && !(WA & 4) && p.d.Cin == 64 && hint_dbg(&p.d) != 72) {      // (the VQ_F16X2 epilogue's fp32 slab is larger; dbg 72 = A/B)
     constexpr size_t ONE = (size_t)PMAX * 8 * 64 * sizeof(vq_bf16), EPI = (size_t)BP * BC * sizeof(vq_bf16);
     lds_bytes = ONE > EPI ? ONE : EPI;
   }
@@ -2560,6 +2674,33 @@ static bool tap3_eligible(const VqConvDesc* d) {
          d->pad_l == 1 && d->Ho == d->H * d->up && d->Wo == d->W * d->up && d->Wo >= 16 && ilog2_exact(d->Wo) >= 0;
 }
 
+// The nine-tap kernel as a 128-channel x 256-pixel tile — one 16 x 16 patch, 2 x 2 waves of 64c x 128p, ONE halo buffer (64 KiB of
+// LDS with the epilogue's slab: two blocks per CU) — where dispatch_glds would run the 128 x 128 nine-tap tile.  A 64c x 128p wave
+// issues 8 MFMAs per 2 KiB of weight fragments where the 64c x 64p wave issues 4.  dbg 80 forces it wherever the shape admits it,
+// dbg 88 keeps the 128 x 128 tile (tests, A/B on one library).  Its GroupNorm partial rows are the 128 x 128 tile's (32 pixels each,
+// same sums in the same order): vq_conv2d_gn_tile, the partial buffer and the statistics do not depend on which of the two runs.
+static bool tap9_wide_auto(const VqConvDesc* d);
+static bool tap9_wide(const VqConvDesc* d) {
+  const int knob = hint_tile(d) & 7, dbg = hint_dbg(d);
+  if (d->dtype != VQ_BF16 && d->dtype != VQ_F16) return false;     // (the VQ_F16X2 epilogue's fp32 slab does not fit)
+  if (!glds_eligible(d) || !(d->Cout > 64 && max_ctile(d) >= 128) || glds_t256(d) || !glds_wreg(d) || !tap9_shape_ok(d)) return false;
+  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
+  const bool small = vq_ceil_div(M, 128) * vq_ceil_div(d->Cout, 128) < 256;       // (dispatch_glds: no nine-tap kernel there unhinted)
+  if (d->Ho % 16 || dbg == 88 || !(knob == 5 || (knob == 0 && !small))) return false;
+  if (dbg == 80) return true;
+  return dbg == 0 && knob == 0 && tap9_wide_auto(d);
+}
+// unhinted: at least two blocks per CU (512 tiles), on the descriptors it measured faster on (MI355X, B = 16, two repeats each,
+// profiles/pr7_tap9_wide_layers.txt; 128 x 128 tile -> this one, TFLOP/s):
+//   128 -> 128 @256^2   bf16 916 -> 1032 fwd, 988 -> 1090 dgrad;  binary16 838 -> 937, 918 -> 1007
+//   256 -> 128 @256^2   bf16 1074 -> 1236;  binary16 1021 -> 1169      (forward; its data gradient is the 128 -> 256 descriptor)
+//   128 -> 128 @128^2   bf16 1043 -> 1152 fwd, 1048 -> 1158 dgrad;  binary16 966 -> 1074, 973 -> 1081
+// NOT on 128 -> 256 @256^2 (two channel tiles over one patch): bf16 1184 -> 1177, binary16 1098 -> 1095 — it keeps the 128 x 128 tile.
+static bool tap9_wide_auto(const VqConvDesc* d) {
+  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
+  return d->Cout <= 128 && (d->Cin == 128 || d->Cin == 256) && M / 256 >= 512;
+}
+
 template <int DT>
 static int dispatch_glds(ConvParams& p, hipStream_t stream) {
   const VqConvDesc* d = &p.d;
@@ -2606,7 +2747,9 @@ static int dispatch_glds(ConvParams& p, hipStream_t stream) {
       // (Round 6: this tile's weight stream — 2 KB per k-step and wave from L2 = the CU's 64 B/clk vector-memory path (its width on CDNA parts as far as we know) for as long as the k-step's four
       // MFMAs last — halved by 8 waves x 64c x 128p over 32 x 16 patches, launch_tap9<DT, 128, 512, 64, 128, 1>: 158 KB of LDS = one
       // block per CU, 256 VGPRs + 228 B of scratch, no register addresses: 26-34 % SLOWER at 128 -> 128 and 256 -> 128 @256^2,
-      // profiles/r6t_tap9_128x512_ab.txt.  Not kept.)
+      // profiles/r6t_tap9_128x512_ab.txt.  Not kept.  The same 64c x 128p wave in a 4-wave tile over ONE 16 x 16 patch with one halo
+      // buffer — 64 KiB, two blocks per CU, 228 VGPRs, register addresses kept — is tap9_wide below: +10-15 % where it runs.)
+      if constexpr (DT != VQ_F16X2) { if (tap9_wide(d)) return launch_tap9<DT, 128, 256, 64, 128, 7>(p, stream); }
       return launch_tap9<DT, 128, 128, 64, 64, 3>(p, stream);
     }
     if (!small) {
@@ -2646,6 +2789,7 @@ static int dispatch_glds(ConvParams& p, hipStream_t stream) {
 
 // pixel tile / wave count of the kernel a GroupNorm-partial-capable descriptor is dispatched to: the 8-wave 256 x 256 tile or one
 // of the 4-wave 128-pixel tiles (the launchers re-check both against their template parameters)
+// (the 4-wave 128 x 256 nine-tap tile, tap9_wide, counts as 128: it writes the rows of the two 128-pixel tiles it covers)
 static int gn_kernel_bp(const VqConvDesc* d) {
   return (glds_eligible(d) && d->Cout > 64 && max_ctile(d) >= 128 && glds_t256(d)) ? 256 : 128;
 }
