@@ -728,7 +728,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, vq_bf16* lds
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[u][e] = mv[e] > 0.f ? v[u][e] : 0.f;
       }
-      if (p.gn_part && r == 0 && u == 0) {           // (block-uniform; every lane is live with the partials on: gn_tile_impl)
+      if (p.gn_part && r == 0 && u == 0) {           // (block-uniform; every lane is live with the partials on: ConvPlan.gn_row)
         const int spg = p.gn_cg >= 8 ? p.gn_cg >> 3 : 1, src = (lane % SPRW) & ~(spg - 1);
         gpiv[0] = __shfl(v[0][0], src);
         gpiv[1] = p.gn_cg == 4 ? __shfl(v[0][4], src) : gpiv[0];
@@ -941,7 +941,7 @@ __device__ __forceinline__ void igemm_epilogue_x2(const ConvParams& p, vq_bf16* 
       }
       if (count_range) rng = vq_absmax_bits(rng, v);
       St::store8_nt(p.y, off, v);
-      if (p.gn_part) {                               // (block-uniform, and every lane is live with the partials on: gn_tile_impl)
+      if (p.gn_part) {                               // (block-uniform, and every lane is live with the partials on: ConvPlan.gn_row)
         if (k == 0) {
           const int spg = p.gn_cg >= 8 ? p.gn_cg >> 3 : 1, src = (lane % SPRW) & ~(spg - 1);
           gpiv[0] = __shfl(v[0], src);
@@ -2448,48 +2448,6 @@ static int ilog2_exact(int v) {
   return ((1 << s) == v) ? s : -1;
 }
 
-template <int DT, int SPLIT, int BC, int BP, int WC, int WP, int BK>
-static int launch_conv(ConvParams& p, hipStream_t stream) {
-  if (p.gn_part && (p.gn_bp != BP || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
-  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
-  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
-  p.Kp = vq_round_up(p.RS * p.d.Cin, 64);
-  const int grid = p.n_ctiles * p.n_ptiles;
-  hipLaunchKernelGGL((conv_igemm_kernel<DT, SPLIT, BC, BP, WC, WP, BK>), dim3(grid), dim3(256), 0, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd");
-  return VQ_OK;
-}
-
-// Tallest row tile a descriptor admits: in sub-pixel mode the rows of a block must lie in ONE phase block (the block's
-// window shift is uniform), so the tile height has to divide Cout/4 (a multiple of 32, checked in vq_conv2d_fwd).
-static int max_ctile(const VqConvDesc* d) {
-  if (!d->subpix) return 256;
-  const int c = d->Cout / 4;
-  return c % 256 == 0 ? 256 : (c % 128 == 0 ? 128 : (c % 64 == 0 ? 64 : 32));
-}
-
-template <int DT, int SPLIT, int BK>
-static int dispatch_tile(ConvParams& p, hipStream_t stream) {
-  const int mct = max_ctile(&p.d);
-  if (p.d.Cout > 64 && mct >= 128) return launch_conv<DT, SPLIT, 128, 128, 64, 64, BK>(p, stream);
-  if (p.d.Cout > 32 && mct >= 64) return launch_conv<DT, SPLIT, 64, 128, 32, 64, BK>(p, stream);
-  return launch_conv<DT, SPLIT, 32, 128, 32, 32, BK>(p, stream);
-}
-
-template <int DT, int BC, int BP, int WC, int WP, int WREG, int DBG = 0, int PP = 0>
-static int launch_glds(ConvParams& p, hipStream_t stream) {
-  if (p.gn_part && (p.gn_bp != BP || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
-  constexpr int NW = (BC / WC) * (BP / WP);
-  constexpr size_t LDS_BYTES = (size_t)2 * ((WREG ? 0 : BC) + BP) * 64 * sizeof(vq_bf16);
-  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
-  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
-  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
-  const int grid = p.n_ctiles * p.n_ptiles;
-  VQ_RESERVE_LDS((conv_igemm_glds_kernel<DT, BC, BP, WC, WP, WREG, DBG, PP>), LDS_BYTES, "vq_conv2d_fwd");
-  hipLaunchKernelGGL((conv_igemm_glds_kernel<DT, BC, BP, WC, WP, WREG, DBG, PP>), dim3(grid), dim3(NW * 64), LDS_BYTES, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd(glds)");
-  return VQ_OK;
-}
 // Kernel-selection hint of a descriptor (VqConvDesc.kernel_hint, include/vqhip.h): 0 = the library's own choice — what the product
 // always passes.  Non-zero values travel IN the descriptor (no process-global dispatch state): tests use them to reach every shipped
 // instantiation at small shapes, tools to A/B two shipped kernels on one shape.
@@ -2502,18 +2460,18 @@ static int launch_glds(ConvParams& p, hipStream_t stream) {
 //                    (The measured-and-not-adopted KERNELS of rounds 2-3 — 128-row and 128 x 512 patch tiles, the resident-weight
 //                    64-channel kernel; dbg 1024 / 2048 / 4096 / 24 / 8200-8203 — were removed in round 5: they last existed in
 //                    commit a426375, csrc/experimental/conv_igemm_experimental.hip; their measurements are in HISTORY.md.)
-static inline int hint_tile(const VqConvDesc* d) { return d->kernel_hint & 15; }
-static inline int hint_dbg(const VqConvDesc* d) { return (d->kernel_hint >> 4) & 0xfffff; }
-static bool hint_supported(const VqConvDesc* d) {
-  const int t = hint_tile(d) & 7, g = hint_dbg(d);
+struct ConvHint { int knob; bool w_lds; int dbg; };   // bits 0-2 (tile), bit 3 (weights through LDS), bits 4..
+static inline ConvHint decode_hint(int kernel_hint) { return ConvHint{kernel_hint & 7, (kernel_hint & 8) != 0, (kernel_hint >> 4) & 0xfffff}; }
+static bool hint_supported(const ConvHint& h) {
+  const int g = h.dbg;
 #ifdef VQ_ABLATION_KERNELS
-  (void)t;
   return !(g == 1024 || g == 2048 || g == 4096 || g == 24 || (g >= 8200 && g <= 8203));      // the removed kernels' hints
 #else
-  return t != 4 && (g == 0 || g == 512 || g == 16 || g == 40 || g == 48 || g == 56 || g == 72 || g == 80 || g == 88);
+  return h.knob != 4 && (g == 0 || g == 512 || g == 16 || g == 40 || g == 48 || g == 56 || g == 72 || g == 80 || g == 88);
 #endif
 }
 
+// ---- shape predicates: each defined once, asked by conv_plan (and by the entry points where a query answers before the plan)
 // data gradient of a patch conv (kernel == stride, no padding: the PatchDiscriminator heads, utils.py:156-185), as
 // ops.conv_dgrad_raw describes it: a stride-1 conv over the R-fold zero-dilated dy with full padding.  Every output
 // pixel has exactly ONE live tap, so it is run as a 1x1 conv dy[Cout] -> [R*S*Cin] with a depth-to-space store
@@ -2522,133 +2480,23 @@ static bool is_patch_dgrad(const VqConvDesc* d) {
   return d->dil_in > 1 && d->dil_in == d->R && d->R == d->S && d->stride == 1 && d->up == 1 && d->pad_t == d->R - 1 &&
          d->pad_l == d->S - 1 && d->Ho == d->H * d->R && d->Wo == d->W * d->S && d->split == 1;
 }
+// ... the 1x1 conv over the (small) dy image it runs as: rows = (tap, ci); the caller stores depth-to-space (d2s = R, d2s_c = Cout)
+static VqConvDesc patch_dgrad_as_1x1(const VqConvDesc& d) {
+  VqConvDesc pd = d;
+  pd.Ho = d.H; pd.Wo = d.W; pd.Cout = pd.Cout_w = d.R * d.S * d.Cout; pd.R = pd.S = 1; pd.dil_in = 1; pd.pad_t = pd.pad_l = 0;
+  return pd;
+}
 static bool glds_eligible(const VqConvDesc* d) { return dt16(d->dtype) && d->split == 1 && d->Cin % 64 == 0; }
-static bool glds_t256(const VqConvDesc* d) {
-  const int tile = hint_tile(d) & 7;
-  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-  if (tile == 5 && d->R == 3 && d->S == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->dil_in == 1 && d->subpix == 0 &&
-      d->Ho == d->H * d->up && d->Wo == d->W * d->up && d->Wo % 16 == 0 && d->Ho % 8 == 0)
-    return false;   // nine-tap kernel forced (128-row tiles, register weights)
-  return d->Cout > 64 && max_ctile(d) >= 256 &&
-         (tile == 3 || ((tile == 0 || tile == 4) && d->Cout % 256 == 0 && (M >= 32768 || tile == 4)));
+// Tallest row tile a descriptor admits: in sub-pixel mode the rows of a block must lie in ONE phase block (the block's
+// window shift is uniform), so the tile height has to divide Cout/4 (a multiple of 32, checked in vq_conv2d_fwd).
+static int max_ctile(const VqConvDesc* d) {
+  if (!d->subpix) return 256;
+  const int c = d->Cout / 4;
+  return c % 256 == 0 ? 256 : (c % 128 == 0 ? 128 : (c % 64 == 0 ? 64 : 32));
 }
-// direct-to-register weights: the 128x128 and 64x128 tiles (waves own disjoint, or at most pairwise shared,
-// weight rows), except 1x1 convs (measured slower).  The 32x128 tile (4 waves on the same 32 rows) and the
-// 256x256 tile keep the LDS path.
-static bool tap9_shape_ok(const VqConvDesc* d);
-// 3x3 layers with at most 32 (padded) output channels on large images — decoder.conv_out (128 -> 3), the data gradient of VGG
-// conv1_1 (64 -> 3): HBM-bound layers that the one-tap 32-row tile ran at 1.5-2.4 TB/s of INPUT traffic because it staged the
-// pixel tile once per tap (nine times the input through L2 -> LDS).  The nine-tap kernel stages it once.  hint 5 = at any size,
-// dbg 40 = A/B against the one-tap tile.
-static bool tap9_rows32(const VqConvDesc* d) {
-  const int knob = hint_tile(d) & 7;
-  return d->Cout <= 32 && d->Cin % 64 == 0 && tap9_shape_ok(d) && !is_patch_dgrad(d) &&
-         (knob == 5 || (knob == 0 && hint_dbg(d) != 40 && (int64_t)d->N * d->Ho * d->Wo >= (int64_t)512 * 128));
-}
-static bool glds_wreg(const VqConvDesc* d) {
-  return (hint_tile(d) & 8) == 0 && !glds_t256(d) && d->R * d->S > 1 &&
-         ((d->Cout > 32 && max_ctile(d) >= 64) || tap9_rows32(d));
-}
-extern "C" int vq_conv_weight_layout(const VqConvDesc* d0) {
-  if (!d0) return 0;
-  const VqConvDesc dv = x2_virtual(d0);
-  const VqConvDesc* d = &dv;
-  if (is_patch_dgrad(d)) return 2;
-  return (glds_eligible(d) && glds_wreg(d)) ? 1 : 0;
-}
-
-template <int DT, int BC, int BP, int WC, int WP>
-static int launch_tap3(ConvParams& p, hipStream_t stream) {
-  if (p.gn_part && (p.gn_bp != BP || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
-  constexpr int NW = (BC / WC) * (BP / WP);
-  constexpr int PMAX = (BP + 2 * (BP / 16) + 7) / 8;
-  constexpr size_t LDS_BYTES = (size_t)2 * PMAX * 8 * 64 * sizeof(vq_bf16);
-  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16), "the epilogue transposes the output tile through the same LDS");
-  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
-  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
-  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
-  const int grid = p.n_ctiles * p.n_ptiles;
-  VQ_RESERVE_LDS((conv_igemm_tap3_kernel<DT, BC, BP, WC, WP>), LDS_BYTES, "vq_conv2d_fwd");
-  hipLaunchKernelGGL((conv_igemm_tap3_kernel<DT, BC, BP, WC, WP>), dim3(grid), dim3(NW * 64), LDS_BYTES, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd(tap3)");
-  return VQ_OK;
-}
-template <int DT, int BC, int BP, int WC, int WP, int WA = 0>
-static int launch_tap9(ConvParams& p, hipStream_t stream) {
-  // (WA & 4: the 256-pixel tile writes the partial rows of its two 128-pixel halves, igemm_epilogue GN2)
-  if (p.gn_part && (p.gn_bp != ((WA & 4) ? BP / 2 : BP) || p.gn_nw != (BC / WC) * (BP / WP))) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, (BC / WC) * (BP / WP)); return VQ_ERR_UNSUPPORTED; }
-  constexpr int NW = (BC / WC) * (BP / WP);
-  constexpr int PMAX = ((BP / 16 + 2) * 18 + 7) / 8;
-  constexpr size_t HALO_BYTES = (size_t)PMAX * 8 * 64 * sizeof(vq_bf16), EPI_BYTES = (size_t)BP * BC * sizeof(vq_bf16);
-  // (WA & 4: one halo buffer, or the epilogue's slab where that is larger)
-  constexpr size_t LDS_BYTES = (WA & 4) ? (HALO_BYTES > EPI_BYTES ? HALO_BYTES : EPI_BYTES)
-                                        : ((WA & 2) ? (size_t)32768 : HALO_BYTES) + HALO_BYTES;
-  static_assert(!(WA & 4) || (DT != VQ_F16X2 && 2 * LDS_BYTES <= 160 * 1024), "the one-buffer form: two blocks per CU, no fp32 epilogue slab");
-  if ((WA & 4) && ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin >= ((int64_t)1 << 31) || (int64_t)vq_round_up(p.d.Cout, 32) * p.Kp >= ((int64_t)1 << 31))) {
-    vq_set_error("vq_conv2d_fwd(tap9): input or packed weights of 2^31 elements or more");
-    return VQ_ERR_UNSUPPORTED;
-  }
-  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16), "the epilogue transposes the output tile through the same LDS");
-  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
-  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
-  p.n_ptiles = p.M / BP;
-  p.pt_tx = p.d.Wo / 16;
-  p.pt_tpi = p.pt_tx * (p.d.Ho / (BP / 16));
-  const int grid = p.n_ctiles * p.n_ptiles;
-  VQ_RESERVE_LDS((conv_igemm_tap9_kernel<DT, BC, BP, WC, WP, WA>), LDS_BYTES, "vq_conv2d_fwd");
-  // A single 64-channel chunk (Cin = 64: VGG conv1_2, the 64-channel levels of the reference's own launch line) never touches the
-  // second halo buffer: launched with the first one alone (>= the epilogue's transposition slab), so that the LDS no longer caps
-  // the kernel at two blocks per CU (four fit its 123 VGPRs).  A K = 576 tile is short — 72 MFMAs per wave between a halo DMA that
-  // must land first and an epilogue — and more resident blocks are what covers those two ends: forward +10-18 %, data gradient +5-8 %
-  // (profiles/r6e_c64_onebuf_ab.txt; a deeper weight-fragment ring instead: +-1 %, r6f_tap9_wd_ab.txt).
-  size_t lds_bytes = LDS_BYTES;
-  if (DT != VQ_F16X2 && !(WA & 4) && p.d.Cin == 64 && hint_dbg(&p.d) != 72) {      // (the VQ_F16X2 epilogue's fp32 slab is larger; dbg 72 = A/B)
-    constexpr size_t ONE = (size_t)PMAX * 8 * 64 * sizeof(vq_bf16), EPI = (size_t)BP * BC * sizeof(vq_bf16);
-    lds_bytes = ONE > EPI ? ONE : EPI;
-  }
-  hipLaunchKernelGGL((conv_igemm_tap9_kernel<DT, BC, BP, WC, WP, WA>), dim3(grid), dim3(NW * 64), lds_bytes, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd(tap9)");
-  return VQ_OK;
-}
-template <int DT, int BC = 256, int S = 3>
-static int launch_p9(ConvParams& p, hipStream_t stream) {
-  constexpr int BP = 256, NW = 8;
-  if (p.gn_part && (p.gn_bp != BP || p.gn_nw != NW)) { vq_set_error("vq_conv2d_fwd: GroupNorm partial tile %d x %d rows != kernel tile %d pixels x %d waves", p.gn_bp, p.gn_nw, BP, NW); return VQ_ERR_UNSUPPORTED; }
-  constexpr int PMAX = (18 * 18 + 7) / 8;
-  constexpr size_t LDS_BYTES = (size_t)2 * BC * 64 * sizeof(vq_bf16) + (size_t)2 * PMAX * 8 * 64 * sizeof(vq_bf16);
-  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16) && LDS_BYTES <= 160 * 1024, "epilogue transpose / LDS capacity");
-  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
-  if ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin >= ((int64_t)1 << 31)) { vq_set_error("vq_conv2d_fwd(p9): input of 2^31 elements or more"); return VQ_ERR_UNSUPPORTED; }
-  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);
-  p.n_ptiles = p.M / BP;
-  p.pt_tx = p.d.Wo / 16;
-  p.pt_tpi = p.pt_tx * (p.d.Ho / 16);
-  const int grid = p.n_ctiles * p.n_ptiles;
-  VQ_RESERVE_LDS((conv_igemm_p9_kernel<DT, BC, S>), LDS_BYTES, "vq_conv2d_fwd");
-  hipLaunchKernelGGL((conv_igemm_p9_kernel<DT, BC, S>), dim3(grid), dim3(NW * 64), LDS_BYTES, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd(p9)");
-  return VQ_OK;
-}
-// conv_patch_dgrad_kernel: patch-conv data gradients (ConvParams already rewritten to the 1x1 form by vq_conv2d_fwd) with 32 or 64
-// channels of dy, whole 128-row / 128-pixel tiles (template parameter KS = K / 16)
-static bool patch_dgrad_persistent_ok(const ConvParams& p) {
-  // (K = 64 — the 128 -> 64 head — was measured too: 69 vs 55 us on the LDS-DMA tile kernel, whose staging reads whole 128-byte
-  // rows where this kernel's fragment loads touch a quarter of every row per instruction: profiles/r3e_patch_dgrad_micro.txt)
-  return p.d.dtype != VQ_F16X2 && p.d2s > 0 && !p.sub && p.d.Cin == 32 && p.d.Cout % 128 == 0 && p.M % 128 == 0 && !p.gn_part &&
-         (hint_tile(&p.d) & 7) == 0 && hint_dbg(&p.d) != 48 && (p.M >= 128 * 64 || hint_dbg(&p.d) == 56);    // dbg 56: at any size (tests)
-}
-template <int DT>
-static int launch_patch_dgrad(ConvParams& p, hipStream_t stream) {
-  constexpr size_t LDS_BYTES = (size_t)128 * 128 * sizeof(vq_bf16);
-  p.n_ctiles = p.d.Cout / 128;
-  p.n_ptiles = p.M / 128;
-  p.pt_tx = 0; p.pt_tpi = 0;
-  // two blocks per CU, every row tile the same number of pixel-tile ranges
-  const int groups = std::max(1, std::min(512 / p.n_ctiles, p.n_ptiles / 4));
-  const int grid = groups * p.n_ctiles;
-  hipLaunchKernelGGL((conv_patch_dgrad_kernel<DT, 2>), dim3(grid), dim3(256), LDS_BYTES, stream, p);
-  VQ_CHECK_LAUNCH("vq_conv2d_fwd(patch dgrad)");
-  return VQ_OK;
+// 3x3 / stride 1 / pad 1 with an output the size of the input (behind the nearest-2x gather: twice that) — forward or data gradient
+static bool conv3x3_same(const VqConvDesc* d) {
+  return d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 && d->pad_t == 1 && d->pad_l == 1 && d->Ho == d->H * d->up && d->Wo == d->W * d->up;
 }
 // conv_igemm_tap9_kernel: 3x3 / stride 1 / pad 1 convs (also behind the nearest-2x gather, also as data gradients) whose
 // output splits into 8 x 16 patches.  Measured (profiles/r1_tap9_v35.txt, B = 16): as 2 x 2 waves of 64c x 64p it beats
@@ -2657,10 +2505,7 @@ static int launch_patch_dgrad(ConvParams& p, hipStream_t stream) {
 // 1105 vs 1016) — so it takes over exactly where those two ran.  As 4 waves x 32c x 128p (every wave reads all 128 pixels'
 // fragments from LDS) the 6x smaller DMA volume bought nothing (737 / 843 / 893 / 864): LDS fragment reads, not the fill,
 // bound these tiles.
-static bool tap9_shape_ok(const VqConvDesc* d) {
-  return d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 && d->pad_t == 1 && d->pad_l == 1 && d->Ho == d->H * d->up &&
-         d->Wo == d->W * d->up && d->Wo % 16 == 0 && d->Ho % 8 == 0 && d->subpix == 0;
-}
+static bool tap9_shape_ok(const VqConvDesc* d) { return conv3x3_same(d) && d->Wo % 16 == 0 && d->Ho % 8 == 0 && d->subpix == 0; }
 // the phase-decomposed Upsample forward (VqConvDesc.subpix: 2x2 / stride 1 / pad 1 windows, 4 phase blocks of Cout / 4 rows) on
 // images that split into 16 x 16 patches
 static bool subpix_patch_ok(const VqConvDesc* d) {
@@ -2669,154 +2514,197 @@ static bool subpix_patch_ok(const VqConvDesc* d) {
 }
 // conv_igemm_tap3_kernel: register-weight tiles of 3x3 / stride 1 / pad 1 convs (also behind a nearest-2x upsample,
 // also as the data gradient of such a conv) whose output rows are a power of two >= 16 pixels long
-static bool tap3_eligible(const VqConvDesc* d) {
-  return (hint_tile(d) & 7) != 6 && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 && d->pad_t == 1 &&
-         d->pad_l == 1 && d->Ho == d->H * d->up && d->Wo == d->W * d->up && d->Wo >= 16 && ilog2_exact(d->Wo) >= 0;
-}
+static bool tap3_shape_ok(const VqConvDesc* d) { return conv3x3_same(d) && d->Wo >= 16 && ilog2_exact(d->Wo) >= 0; }
 
-// The nine-tap kernel as a 128-channel x 256-pixel tile — one 16 x 16 patch, 2 x 2 waves of 64c x 128p, ONE halo buffer (64 KiB of
-// LDS with the epilogue's slab: two blocks per CU) — where dispatch_glds would run the 128 x 128 nine-tap tile.  A 64c x 128p wave
-// issues 8 MFMAs per 2 KiB of weight fragments where the 64c x 64p wave issues 4.  dbg 80 forces it wherever the shape admits it,
-// dbg 88 keeps the 128 x 128 tile (tests, A/B on one library).  Its GroupNorm partial rows are the 128 x 128 tile's (32 pixels each,
-// same sums in the same order): vq_conv2d_gn_tile, the partial buffer and the statistics do not depend on which of the two runs.
-static bool tap9_wide_auto(const VqConvDesc* d);
-static bool tap9_wide(const VqConvDesc* d) {
-  const int knob = hint_tile(d) & 7, dbg = hint_dbg(d);
-  if (d->dtype != VQ_BF16 && d->dtype != VQ_F16) return false;     // (the VQ_F16X2 epilogue's fp32 slab does not fit)
-  if (!glds_eligible(d) || !(d->Cout > 64 && max_ctile(d) >= 128) || glds_t256(d) || !glds_wreg(d) || !tap9_shape_ok(d)) return false;
+// ---- the plan: which kernel serves a descriptor, with which packed-weight layout and which GroupNorm partial rows.  Computed once
+// per call by conv_plan; vq_conv2d_fwd launches from it, vq_conv_weight_layout and vq_conv2d_gn_tile read it.
+enum ConvFamily {
+  CONV_NONE = 0,                 // a storage type / split the entry point refuses
+  CONV_C8, CONV_C8_X2,           // conv_small.hip: conv3x3_c8_kernel (3-channel image layers) and its VQ_F16X2 twin
+  CONV_PATCH_DGRAD, CONV_GENERIC,   // conv_patch_dgrad_kernel (persistent);  conv_igemm_kernel<DT, SPLIT, ..., BK>: register-staged tiles, every storage type
+  CONV_GLDS, CONV_TAP3, CONV_TAP9, CONV_P9   // the LDS-DMA kernels (glds_eligible): one tap / three taps / nine taps per staging, 256 x 256 over a patch
+};
+// what selection depends on beside the descriptor: a residual operand is passed (the 8-channel kernels take none); GroupNorm partials are
+// requested (no 64 x 64 three-tap tile, no VQ_F16X2 8-channel kernel); VqConvDesc.gn_bwd is set (no 64 x 64 three-tap tile)
+struct ConvCall { bool residual, gn_partials, gn_bwd; };
+struct ConvPlan {
+  int family;            // ConvFamily
+  int BC, BP, WC, WP;    // block tile (channels x pixels), wave tile; 0 for CONV_C8 / CONV_C8_X2 / CONV_PATCH_DGRAD
+  int v0, v1, v2;        // CONV_GLDS: WREG, DBG, PP;  CONV_TAP9: WA;  CONV_P9: S;  CONV_GENERIC: SPLIT, BK
+  int layout;            // packed weights (pack_weight_kernel): 0 = [row][Kp], 1 = fragment order, 2 = transposed patch
+  int gn_bp, gn_nw, gn_row;   // what the kernel's GroupNorm epilogue writes: pixels per partial tile, rows per tile (one per wave), pixels per row;
+                         // gn_row 0 = it cannot (fp32 storage, the 8-channel image kernels, sub-pixel stores, true channels != padded, tiles that straddle images)
+  ConvHint hint;
+};
+enum { CONV_PLAN_INTS = 12 };   // family .. gn_row, in declaration order (vq_debug_conv_plan)
+// d0: the virtualised descriptor (x2_virtual) as the caller wrote it — a patch data gradient is planned as the 1x1 conv it runs as.
+static ConvPlan conv_plan(const VqConvDesc& d0, const ConvCall& c) {
+  ConvPlan pl = {};
+  const ConvHint h = pl.hint = decode_hint(d0.kernel_hint);
+  const int knob = h.knob, dbg = h.dbg;
+  const bool patch = is_patch_dgrad(&d0);
+  const VqConvDesc v = patch ? patch_dgrad_as_1x1(d0) : d0;
+  const VqConvDesc* d = &v;
+  const bool depth2space = patch || d->subpix;                 // (ConvParams.d2s != 0)
   const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-  const bool small = vq_ceil_div(M, 128) * vq_ceil_div(d->Cout, 128) < 256;       // (dispatch_glds: no nine-tap kernel there unhinted)
-  if (d->Ho % 16 || dbg == 88 || !(knob == 5 || (knob == 0 && !small))) return false;
-  if (dbg == 80) return true;
-  return dbg == 0 && knob == 0 && tap9_wide_auto(d);
-}
-// unhinted: at least two blocks per CU (512 tiles), on the descriptors it measured faster on (MI355X, B = 16, two repeats each,
-// profiles/pr7_tap9_wide_layers.txt; 128 x 128 tile -> this one, TFLOP/s):
-//   128 -> 128 @256^2   bf16 916 -> 1032 fwd, 988 -> 1090 dgrad;  binary16 838 -> 937, 918 -> 1007
-//   256 -> 128 @256^2   bf16 1074 -> 1236;  binary16 1021 -> 1169      (forward; its data gradient is the 128 -> 256 descriptor)
-//   128 -> 128 @128^2   bf16 1043 -> 1152 fwd, 1048 -> 1158 dgrad;  binary16 966 -> 1074, 973 -> 1081
-// NOT on 128 -> 256 @256^2 (two channel tiles over one patch): bf16 1184 -> 1177, binary16 1098 -> 1095 — it keeps the 128 x 128 tile.
-static bool tap9_wide_auto(const VqConvDesc* d) {
-  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-  return d->Cout <= 128 && (d->Cin == 128 || d->Cin == 256) && M / 256 >= 512;
-}
-
-template <int DT>
-static int dispatch_glds(ConvParams& p, hipStream_t stream) {
-  const VqConvDesc* d = &p.d;
-  const int knob = hint_tile(d) & 7, dbg = hint_dbg(d);
-  (void)dbg;
-  const bool wreg = glds_wreg(d);
-  // measured (profiles/r1_tap3_ab_v22.txt): pays on the short-M layers (32x32 and 16x16 images: +11..34 %), not at 256x256
-  const bool tap3 = wreg && p.d2s == 0 && tap3_eligible(d) && (p.M <= 16384 || knob == 7);
-  p.wo_shift = ilog2_exact(p.d.Wo);
   const int mct = max_ctile(d);
-  if (p.d.Cout > 64 && mct >= 128) {
-    // 256x256 tile (8 waves x 128c x 64p, 128 KiB LDS): half the L2->LDS bytes per flop of the 128x128 tile
-#ifdef VQ_ABLATION_KERNELS
-    if (glds_t256(d) && dbg == 8) return launch_glds<DT, 256, 256, 128, 64, 0, 8>(p, stream);
-    if (glds_t256(d) && dbg == 1) return launch_glds<DT, 256, 256, 128, 64, 0, 1>(p, stream);
-    if (glds_t256(d) && knob == 4) return launch_glds<DT, 256, 256, 128, 64, 0, 0, 0>(p, stream);   // A/B: free-running loop
-#endif
-    // 3x3 / stride 1 / pad 1 layers whose images split into 16 x 16 patches: the same tile over a staged patch (nine taps per
-    // staging); dbg 512 = A/B against the one-tap form
-    if (glds_t256(d) && dbg != 512 && p.d2s == 0 && tap9_shape_ok(d) && p.d.Ho % 16 == 0 && p.d.Cin % 64 == 0)
-      return launch_p9<DT>(p, stream);
-    // ... and the sub-pixel Upsample forward (2x2 windows moved by the block's phase) over the same staged patch
-    if (glds_t256(d) && dbg != 512 && subpix_patch_ok(d)) return launch_p9<DT, 256, 2>(p, stream);
-    if (glds_t256(d)) return launch_glds<DT, 256, 256, 128, 64, 0, 0, 1>(p, stream);                                  // ping-pong schedule
-#ifdef VQ_ABLATION_KERNELS   // profiling-only builds (make ABLATE=1): compile-time ablated copies of the 128x128 kernel
-    if (dbg == 8) return launch_glds<DT, 128, 128, 64, 64, 0, 8>(p, stream);   // DMA issued, never waited for (wrong results)
-    if (dbg == 1) return launch_glds<DT, 128, 128, 64, 64, 0, 1>(p, stream);
-    if (dbg == 2) return launch_glds<DT, 128, 128, 64, 64, 0, 2>(p, stream);
-    if (dbg == 3) return launch_glds<DT, 128, 128, 64, 64, 0, 3>(p, stream);
-    if (dbg == 4) return launch_glds<DT, 128, 128, 64, 64, 0, 4>(p, stream);
-#endif
-    // small images (VGG conv5_x at 16x16: M = 4096): 128x128 tiles would leave half of the 256 CUs without a block
-    if (knob == 2) return launch_glds<DT, 32, 128, 32, 32, 0>(p, stream);   // hint: 32x128 tiles
-    const bool small = knob == 0 && vq_ceil_div(p.M, 128) * vq_ceil_div(p.d.Cout, 128) < 256;
-    // nine-tap kernel: automatically where the 128x128 register-weight tile / the three-tap kernel would run with at least
-    // one block per CU; hint 5 forces it wherever the shape allows, hint 6 switches it (and the three-tap kernel) off
-    if (wreg && p.d2s == 0 && tap9_shape_ok(d) && (knob == 5 || (knob == 0 && !small))) {
-      // measured on MI355X (profiles/r2_tap9_variants.txt, B = 16, bf16): WA = 3 vs the round-1 form +4..6 % at 128 channels /
-      // 256x256, +11..15 % at 512 channels / 32x32; WA = 1 alone: no gain (202 VGPRs: one wave per SIMD fewer)
-#ifdef VQ_ABLATION_KERNELS
-      if (dbg == 64) return launch_tap9<DT, 128, 128, 32, 128>(p, stream);
-      if (dbg == 128) return launch_tap9<DT, 128, 128, 64, 64, 0>(p, stream);      // the round-1 form
-#endif
-      // (Round 6: this tile's weight stream — 2 KB per k-step and wave from L2 = the CU's 64 B/clk vector-memory path (its width on CDNA parts as far as we know) for as long as the k-step's four
-      // MFMAs last — halved by 8 waves x 64c x 128p over 32 x 16 patches, launch_tap9<DT, 128, 512, 64, 128, 1>: 158 KB of LDS = one
-      // block per CU, 256 VGPRs + 228 B of scratch, no register addresses: 26-34 % SLOWER at 128 -> 128 and 256 -> 128 @256^2,
-      // profiles/r6t_tap9_128x512_ab.txt.  Not kept.  The same 64c x 128p wave in a 4-wave tile over ONE 16 x 16 patch with one halo
-      // buffer — 64 KiB, two blocks per CU, 228 VGPRs, register addresses kept — is tap9_wide below: +10-15 % where it runs.)
-      if constexpr (DT != VQ_F16X2) { if (tap9_wide(d)) return launch_tap9<DT, 128, 256, 64, 128, 7>(p, stream); }
-      return launch_tap9<DT, 128, 128, 64, 64, 3>(p, stream);
+  const bool big = d->Cout > 64 && mct >= 128, mid = d->Cout > 32 && mct >= 64;   // row tiles of 128 (256) / 64 channels are admitted
+  const bool lds_dma = glds_eligible(d), t9 = tap9_shape_ok(d);
+  // the 256x256 tile (8 waves x 128c x 64p, 128 KiB LDS): half the L2->LDS bytes per flop of the 128x128 tile;  hint 5 = nine-tap
+  // kernel forced (128-row tiles, register weights)
+  const bool t256 = lds_dma && !(knob == 5 && t9) && d->Cout > 64 && mct >= 256 &&
+                    (knob == 3 || ((knob == 0 || knob == 4) && d->Cout % 256 == 0 && (M >= 32768 || knob == 4)));
+  // 3x3 layers with at most 32 (padded) output channels on large images — decoder.conv_out (128 -> 3), the data gradient of VGG
+  // conv1_1 (64 -> 3): HBM-bound layers that the one-tap 32-row tile ran at 1.5-2.4 TB/s of INPUT traffic because it staged the
+  // pixel tile once per tap (nine times the input through L2 -> LDS).  The nine-tap kernel stages it once.  hint 5 = at any size,
+  // dbg 40 = A/B against the one-tap tile.
+  const bool rows32 = lds_dma && d->Cout <= 32 && t9 && (knob == 5 || (knob == 0 && dbg != 40 && M >= (int64_t)512 * 128));
+  // direct-to-register weights: the 128x128 and 64x128 tiles (waves own disjoint, or at most pairwise shared,
+  // weight rows), except 1x1 convs (measured slower).  The 32x128 tile (4 waves on the same 32 rows) and the
+  // 256x256 tile keep the LDS path.  THIS is what the weights are packed by (layout 1), whichever tile then runs.
+  const bool wreg = lds_dma && !h.w_lds && !t256 && d->R * d->S > 1 && (mid || rows32);
+  // three-tap kernel — measured (profiles/r1_tap3_ab_v22.txt): pays on the short-M layers (32x32 and 16x16 images: +11..34 %), not at 256x256
+  const bool tap3 = wreg && !depth2space && knob != 6 && tap3_shape_ok(d) && (M <= 16384 || knob == 7);
+  const auto use = [&pl](int family, int BC = 0, int BP = 0, int WC = 0, int WP = 0, int v0 = 0, int v1 = 0, int v2 = 0) {
+    pl.family = family; pl.BC = BC; pl.BP = BP; pl.WC = WC; pl.WP = WP; pl.v0 = v0; pl.v1 = v1; pl.v2 = v2;
+  };
+  const auto choose = [&]() -> void {
+    const bool plain16 = d->dtype == VQ_BF16 || d->dtype == VQ_F16;
+    if (dt16(d->dtype) ? d->split != 1 : !(d->dtype == VQ_F32 && (d->split == 1 || d->split == 3 || d->split == 6))) return use(CONV_NONE);
+    // 3-channel image layers (the VQ_F16X2 8-channel kernel forms no GroupNorm partials)
+    if (plain16 && vq_conv_c8_shape(d) && !c.residual) return use(CONV_C8);
+    if (d->dtype == VQ_F16X2 && !c.gn_partials && vq_conv_c8_x2_shape(d) && !c.residual) return use(CONV_C8_X2);
+    // conv_patch_dgrad_kernel: patch-conv data gradients with 32 channels of dy, whole 128-row / 128-pixel tiles
+    // (K = 64 — the 128 -> 64 head — was measured too: 69 vs 55 us on the LDS-DMA tile kernel, whose staging reads whole 128-byte
+    // rows where this kernel's fragment loads touch a quarter of every row per instruction: profiles/r3e_patch_dgrad_micro.txt)
+    const bool persistent = plain16 && patch && d->Cin == 32 && d->Cout % 128 == 0 && M % 128 == 0 && !c.gn_partials && knob == 0 && dbg != 48;
+    if (persistent && (M >= 128 * 64 || dbg == 56)) return use(CONV_PATCH_DGRAD);                      // dbg 56: at any size (tests)
+    if (!lds_dma) {
+      // (split 3: 16-wide chunks measured: 33.8 vs 43.9 img/s, profiles/r4h_*;  split 6, three planes per operand: 16-wide chunks keep
+      // the tile in 48 KiB)
+      const int bk = d->split == 1 ? 64 : d->split == 3 ? 32 : 16;
+      if (big) return use(CONV_GENERIC, 128, 128, 64, 64, d->split, bk);
+      if (mid) return use(CONV_GENERIC, 64, 128, 32, 64, d->split, bk);
+      return use(CONV_GENERIC, 32, 128, 32, 32, d->split, bk);
     }
-    if (!small) {
-      if (tap3) return launch_tap3<DT, 128, 128, 32, 128>(p, stream);
-#ifdef VQ_ABLATION_KERNELS
-      // A/B candidate (dbg 32): the register-weight one-tap tile as 2 x 2 waves of 64c x 64p
-      if (wreg && dbg == 32) return launch_glds<DT, 128, 128, 64, 64, 1>(p, stream);
-#endif
-      if (wreg) return launch_glds<DT, 128, 128, 32, 128, 1>(p, stream);
-      return launch_glds<DT, 128, 128, 64, 64, 0>(p, stream);
+    // (dbg 1-4 / 8 / 32 / 64 / 128 / 256 and hint 4 name compile-time ablated copies and A/B candidates of `make ABLATE=1` builds: a release
+    // library refuses them in hint_supported before it launches; layout and partial rows are the same with or without them)
+    if (big && t256) {
+      if (dbg == 8 || dbg == 1) return use(CONV_GLDS, 256, 256, 128, 64, 0, dbg);
+      if (knob == 4) return use(CONV_GLDS, 256, 256, 128, 64, 0, 0, 0);   // A/B: free-running loop
+      // 3x3 / stride 1 / pad 1 layers whose images split into 16 x 16 patches: the same tile over a staged patch (nine taps per
+      // staging); dbg 512 = A/B against the one-tap form
+      if (dbg != 512 && !depth2space && t9 && d->Ho % 16 == 0) return use(CONV_P9, 256, 256, 128, 64, 3);
+      // ... and the sub-pixel Upsample forward (2x2 windows moved by the block's phase) over the same staged patch
+      if (dbg != 512 && subpix_patch_ok(d)) return use(CONV_P9, 256, 256, 128, 64, 2);
+      return use(CONV_GLDS, 256, 256, 128, 64, 0, 0, 1);                                  // ping-pong schedule
     }
+    if (big) {
+      // profiling-only: compile-time ablated copies of the 128x128 kernel (dbg 8: DMA issued, never waited for: wrong results)
+      if (dbg == 8 || (dbg >= 1 && dbg <= 4)) return use(CONV_GLDS, 128, 128, 64, 64, 0, dbg);
+      // small images (VGG conv5_x at 16x16: M = 4096): 128x128 tiles would leave half of the 256 CUs without a block
+      if (knob == 2) return use(CONV_GLDS, 32, 128, 32, 32, 0);   // hint: 32x128 tiles
+      const bool small = knob == 0 && vq_ceil_div(M, 128) * vq_ceil_div(d->Cout, 128) < 256;
+      // nine-tap kernel: automatically where the 128x128 register-weight tile / the three-tap kernel would run with at least
+      // one block per CU; hint 5 forces it wherever the shape allows, hint 6 switches it (and the three-tap kernel) off
+      if (wreg && !depth2space && t9 && (knob == 5 || (knob == 0 && !small))) {
+        // measured on MI355X (profiles/r2_tap9_variants.txt, B = 16, bf16): WA = 3 vs the round-1 form +4..6 % at 128 channels /
+        // 256x256, +11..15 % at 512 channels / 32x32; WA = 1 alone: no gain (202 VGPRs: one wave per SIMD fewer)
+        if (dbg == 64) return use(CONV_TAP9, 128, 128, 32, 128, 0);
+        if (dbg == 128) return use(CONV_TAP9, 128, 128, 64, 64, 0);      // the round-1 form
+        // (Round 6: this tile's weight stream — 2 KB per k-step and wave from L2 = the CU's 64 B/clk vector-memory path (its width on CDNA parts as far as we know) for as long as the k-step's four
+        // MFMAs last — halved by 8 waves x 64c x 128p over 32 x 16 patches, launch_tap9<DT, 128, 512, 64, 128, 1>: 158 KB of LDS = one
+        // block per CU, 256 VGPRs + 228 B of scratch, no register addresses: 26-34 % SLOWER at 128 -> 128 and 256 -> 128 @256^2,
+        // profiles/r6t_tap9_128x512_ab.txt.  Not kept.  The same 64c x 128p wave in a 4-wave tile over ONE 16 x 16 patch with one halo
+        // buffer — 64 KiB, two blocks per CU, 228 VGPRs, register addresses kept — is the wide tile below: +10-15 % where it runs.)
+        // The nine-tap kernel as a 128-channel x 256-pixel tile — one 16 x 16 patch, 2 x 2 waves of 64c x 128p, ONE halo buffer (64 KiB
+        // of LDS with the epilogue's slab: two blocks per CU) — where the 128 x 128 nine-tap tile would run.  A 64c x 128p wave issues
+        // 8 MFMAs per 2 KiB of weight fragments where the 64c x 64p wave issues 4.  dbg 80 forces it wherever the shape admits it,
+        // dbg 88 keeps the 128 x 128 tile (tests, A/B on one library).  Its GroupNorm partial rows are the 128 x 128 tile's (WA & 4:
+        // rows of BP / 2 pixels' tiles, 32 pixels each, same sums in the same order): vq_conv2d_gn_tile, the partial buffer and the
+        // statistics do not depend on which of the two runs.  Not VQ_F16X2: the epilogue's fp32 slab does not fit.
+        // Unhinted: at least two blocks per CU (512 tiles), on the descriptors it measured faster on (MI355X, B = 16, two repeats each,
+        // profiles/pr7_tap9_wide_layers.txt; 128 x 128 tile -> this one, TFLOP/s):
+        //   128 -> 128 @256^2   bf16 916 -> 1032 fwd, 988 -> 1090 dgrad;  binary16 838 -> 937, 918 -> 1007
+        //   256 -> 128 @256^2   bf16 1074 -> 1236;  binary16 1021 -> 1169      (forward; its data gradient is the 128 -> 256 descriptor)
+        //   128 -> 128 @128^2   bf16 1043 -> 1152 fwd, 1048 -> 1158 dgrad;  binary16 966 -> 1074, 973 -> 1081
+        // NOT on 128 -> 256 @256^2 (two channel tiles over one patch): bf16 1184 -> 1177, binary16 1098 -> 1095 — it keeps the 128 x 128 tile.
+        const bool wide_auto = d->Cout <= 128 && (d->Cin == 128 || d->Cin == 256) && M / 256 >= 512;
+        if (plain16 && d->Ho % 16 == 0 && dbg != 88 && (dbg == 80 || (dbg == 0 && knob == 0 && wide_auto)))
+          return use(CONV_TAP9, 128, 256, 64, 128, 7);
+        return use(CONV_TAP9, 128, 128, 64, 64, 3);
+      }
+      if (!small) {
+        if (tap3) return use(CONV_TAP3, 128, 128, 32, 128);
+        // A/B candidate (dbg 32): the register-weight one-tap tile as 2 x 2 waves of 64c x 64p
+        if (wreg && dbg == 32) return use(CONV_GLDS, 128, 128, 64, 64, 1);
+        if (wreg) return use(CONV_GLDS, 128, 128, 32, 128, 1);
+        return use(CONV_GLDS, 128, 128, 64, 64, 0);
+      }
+    }
+    // the nine-tap kernel as a 64-row tile, 4 waves x 64c x 32p (VGG conv1_2, 64 -> 64 at 256x256): measured +17..18 % forward and
+    // data gradient over the one-tap register-weight tile (profiles/r2_tap9_variants.txt); hint 5 forces it
+    if (mid && wreg && !depth2space && t9 && (knob == 5 || (knob == 0 && dbg != 128 && vq_ceil_div(M, 128) >= 512))) {
+      if (dbg == 256) return use(CONV_TAP9, 64, 128, 64, 32, 0);
+      // (Round 6: the same tile over 16 x 16 patches as 4 waves x 64c x 64p — launch_tap9<DT, 64, 256, 64, 64, 1>, half the weight bytes
+      // every wave pulls from L2 per pixel, 84 KB of LDS = one block per CU — measured 3-6 % SLOWER forward and data gradient at
+      // 64 -> 64 @512^2 (B = 12) in bf16 and binary16, profiles/r6d_c64_ab.txt: the weight stream is not what bounds this tile.  Not kept.)
+      return use(CONV_TAP9, 64, 128, 64, 32, 3);
+    }
+    // Short-M layers (VGG conv5_x: 512 channels at 16 x 16, M = 4096 at B = 16): 64 x 128 tiles are 256 four-wave blocks — ONE wave per
+    // SIMD, nothing to hide an LDS or weight-fetch latency under (measured 290-300 TFLOP/s).  64 x 64 tiles (4 waves x 32c x 32p) put
+    // two blocks on every CU.  dbg 16 = A/B against the 128-pixel tile.  (Not with GroupNorm partials or the fused GroupNorm-backward
+    // sums: their row length is the tile's, 16 pixels per wave here and 32 everywhere else.)
+    if (mid && tap3 && !c.gn_partials && !c.gn_bwd && knob == 0 && dbg != 16 && vq_ceil_div(M, 128) * vq_ceil_div(d->Cout, 64) <= 256)
+      return use(CONV_TAP3, 64, 64, 32, 32);
+    if (mid && tap3) return use(CONV_TAP3, 64, 128, 32, 64);
+    if (mid) return use(CONV_GLDS, 64, 128, 32, 64, wreg ? 1 : 0);
+    if (wreg && rows32) return use(CONV_TAP9, 32, 128, 32, 32, 3);   // (register weights: see wreg)
+    return use(CONV_GLDS, 32, 128, 32, 32, 0);   // (Cout <= 32, or phase blocks of 32 / 96 / ... channels)
+  };
+  choose();
+  pl.layout = patch ? 2 : (wreg ? 1 : 0);
+  if (pl.family >= CONV_GENERIC) {
+    // (WA & 4: the 256-pixel nine-tap tile writes the partial rows of its two 128-pixel halves, igemm_epilogue GN2)
+    pl.gn_bp = (pl.family == CONV_TAP9 && (pl.v0 & 4)) ? pl.BP / 2 : pl.BP;
+    pl.gn_nw = (pl.BC / pl.WC) * (pl.BP / pl.WP);
+    // (16-bit Cin == 8 3x3: every such descriptor, whether or not the 8-channel kernel takes it — an answer kept from before the plan)
+    const bool can = dt16(d->dtype) && !d->subpix && d->Cout == d->Cout_w && !(d->dtype != VQ_F16X2 && d->Cin == 8 && d->R == 3 && d->S == 3) &&
+                     !vq_conv_c8_x2_shape(d) && ((int64_t)d->Ho * d->Wo) % pl.gn_bp == 0;
+    pl.gn_row = can ? pl.gn_bp / pl.gn_nw : 0;
   }
-  // the nine-tap kernel as a 64-row tile, 4 waves x 64c x 32p (VGG conv1_2, 64 -> 64 at 256x256): measured +17..18 % forward and
-  // data gradient over the one-tap register-weight tile (profiles/r2_tap9_variants.txt); hint 5 forces it
-  if (p.d.Cout > 32 && mct >= 64 && wreg && p.d2s == 0 && tap9_shape_ok(d) &&
-      (knob == 5 || (knob == 0 && dbg != 128 && vq_ceil_div(p.M, 128) >= 512))) {
-#ifdef VQ_ABLATION_KERNELS
-    if (dbg == 256) return launch_tap9<DT, 64, 128, 64, 32, 0>(p, stream);
-#endif
-    // (Round 6: the same tile over 16 x 16 patches as 4 waves x 64c x 64p — launch_tap9<DT, 64, 256, 64, 64, 1>, half the weight bytes
-    // every wave pulls from L2 per pixel, 84 KB of LDS = one block per CU — measured 3-6 % SLOWER forward and data gradient at
-    // 64 -> 64 @512^2 (B = 12) in bf16 and binary16, profiles/r6d_c64_ab.txt: the weight stream is not what bounds this tile.  Not kept.)
-    return launch_tap9<DT, 64, 128, 64, 32, 3>(p, stream);
-  }
-  // Short-M layers (VGG conv5_x: 512 channels at 16 x 16, M = 4096 at B = 16): 64 x 128 tiles are 256 four-wave blocks — ONE wave per
-  // SIMD, nothing to hide an LDS or weight-fetch latency under (measured 290-300 TFLOP/s).  64 x 64 tiles (4 waves x 32c x 32p) put
-  // two blocks on every CU.  dbg 16 = A/B against the 128-pixel tile.  (Not with GroupNorm partials: their row length is the tile's.)
-  if (p.d.Cout > 32 && mct >= 64 && tap3 && !p.gn_part && !p.gnb && knob == 0 && dbg != 16 &&
-      vq_ceil_div(p.M, 128) * vq_ceil_div(p.d.Cout, 64) <= 256)
-    return launch_tap3<DT, 64, 64, 32, 32>(p, stream);
-  if (p.d.Cout > 32 && mct >= 64 && tap3) return launch_tap3<DT, 64, 128, 32, 64>(p, stream);
-  if (p.d.Cout > 32 && mct >= 64)
-    return wreg ? launch_glds<DT, 64, 128, 32, 64, 1>(p, stream) : launch_glds<DT, 64, 128, 32, 64, 0>(p, stream);
-  if (wreg && tap9_rows32(d)) return launch_tap9<DT, 32, 128, 32, 32, 3>(p, stream);   // (register weights: see glds_wreg)
-  return launch_glds<DT, 32, 128, 32, 32, 0>(p, stream);   // (Cout <= 32, or phase blocks of 32 / 96 / ... channels)
+  return pl;
 }
+#ifdef VQ_ABLATION_KERNELS
+// tests only (like vq_debug_stamps: not in include/vqhip.h, not in a release library): the plan's integers; flags = ConvCall bits
+// (1 residual, 2 gn_partials, 4 gn_bwd) -> CONV_PLAN_INTS, or -1
+extern "C" int vq_debug_conv_plan(const VqConvDesc* d, int flags, int* out, int n) {
+  if (!d || !out || n < CONV_PLAN_INTS) return -1;
+  const ConvPlan pl = conv_plan(x2_virtual(d), ConvCall{(flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0});
+  const int v[CONV_PLAN_INTS] = {pl.family, pl.BC, pl.BP, pl.WC, pl.WP, pl.v0, pl.v1, pl.v2, pl.layout, pl.gn_bp, pl.gn_nw, pl.gn_row};
+  memcpy(out, v, sizeof v);
+  return CONV_PLAN_INTS;
+}
+#endif
 
-// pixel tile / wave count of the kernel a GroupNorm-partial-capable descriptor is dispatched to: the 8-wave 256 x 256 tile or one
-// of the 4-wave 128-pixel tiles (the launchers re-check both against their template parameters)
-// (the 4-wave 128 x 256 nine-tap tile, tap9_wide, counts as 128: it writes the rows of the two 128-pixel tiles it covers)
-static int gn_kernel_bp(const VqConvDesc* d) {
-  return (glds_eligible(d) && d->Cout > 64 && max_ctile(d) >= 128 && glds_t256(d)) ? 256 : 128;
+// ---- queries.  Both assume a call WITHOUT residual and gn_bwd (neither moves the layout or the row length of a descriptor that has one).
+// What Python packs the weights by.  A patch data gradient answers 2 before anything else.
+extern "C" int vq_conv_weight_layout(const VqConvDesc* d) { return d ? conv_plan(x2_virtual(d), ConvCall{false, false, false}).layout : 0; }
+static bool gn_groups_ok(const VqConvDesc* d, int groups) {      // group sizes the epilogues handle: 4 / 8 / 16 / 32 channels
+  const int cg = (groups > 0 && d->Cout % groups == 0) ? d->Cout / groups : 0;
+  return cg == 4 || cg == 8 || cg == 16 || cg == 32;
 }
-static int gn_kernel_waves(int bp) { return bp >= 256 ? 8 : 4; }
-// Pixels per GroupNorm partial ROW (one row per wave of a tile) of the kernel this descriptor is dispatched to, or 0 when its epilogue cannot produce the
-// partials (fp32 storage, the 8-channel image kernels, depth-to-space stores, tiles that straddle images, group sizes other than
-// 4 / 8 / 16 / 32 channels).  MUST mirror dispatch_glds / dispatch_tile: the launchers re-check it.
-static int gn_tile_impl(const VqConvDesc* d, int groups) {       // d: virtualised (x2_virtual)
-  if (!d || groups <= 0 || !dt16(d->dtype) || d->split != 1) return 0;
-  if (d->subpix || is_patch_dgrad(d) || d->Cout != d->Cout_w || d->Cout % groups) return 0;
-  const int cg = d->Cout / groups;
-  if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return 0;
-  if (d->dtype != VQ_F16X2 && d->Cin == 8 && d->R == 3 && d->S == 3) return 0;     // conv_small.hip
-  if (vq_conv_c8_x2_shape(d)) return 0;                                            //   ... its VQ_F16X2 twin
-  const int bp = gn_kernel_bp(d);
-  if (((int64_t)d->Ho * d->Wo) % bp) return 0;
-  return bp / gn_kernel_waves(bp);
-}
+// What Python sizes the partial buffer by: pixels per GroupNorm partial ROW (one row per wave of a tile) of the kernel that serves this descriptor
+// WITH partials requested, or 0 when it cannot produce them (ConvPlan.gn_row; depth-to-space stores; group sizes other than 4 / 8 / 16 / 32 channels).
 extern "C" int vq_conv2d_gn_tile(const VqConvDesc* d, int groups) {
   if (!d) return 0;
   const VqConvDesc dv = x2_virtual(d);
-  return gn_tile_impl(&dv, groups);
+  if (is_patch_dgrad(&dv) || !gn_groups_ok(&dv, groups)) return 0;
+  return conv_plan(dv, ConvCall{false, true, false}).gn_row;
 }
-
 // Rows per image of the fused GroupNorm-backward sums: every kernel a descriptor without depth-to-space output can reach through
-// dispatch_glds / dispatch_tile writes one row per wave = per 32 output pixels (the 64 x 64 short-M tile, 16 pixels per wave, is not
-// dispatched with the sums on); tiles must not straddle images (256 pixels is the largest tile).
+// conv_plan writes one row per wave = per 32 output pixels (the 64 x 64 short-M tile, 16 pixels per wave, is not
+// planned with the sums on); tiles must not straddle images (256 pixels is the largest tile).
 extern "C" int vq_conv2d_gnb_rows(const VqConvDesc* d) {
 #ifndef VQ_ABLATION_KERNELS
   (void)d;
@@ -2830,6 +2718,135 @@ extern "C" int vq_conv2d_gnb_rows(const VqConvDesc* d) {
   return (int)(hw / 32);
 }
 
+// ---- launchers: one per kernel template; tile and variant arrive as template parameters from the tables below
+template <int DT, int SPLIT, int BC, int BP, int WC, int WP, int BK>
+static int launch_conv(ConvParams& p, const ConvPlan&, hipStream_t stream) {
+  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
+  hipLaunchKernelGGL((conv_igemm_kernel<DT, SPLIT, BC, BP, WC, WP, BK>), dim3(p.n_ctiles * p.n_ptiles), dim3(256), 0, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd");
+  return VQ_OK;
+}
+template <int DT, int BC, int BP, int WC, int WP, int WREG, int DBG = 0, int PP = 0>
+static int launch_glds(ConvParams& p, const ConvPlan&, hipStream_t stream) {
+  constexpr int NW = (BC / WC) * (BP / WP);
+  constexpr size_t LDS_BYTES = (size_t)2 * ((WREG ? 0 : BC) + BP) * 64 * sizeof(vq_bf16);
+  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
+  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
+  VQ_RESERVE_LDS((conv_igemm_glds_kernel<DT, BC, BP, WC, WP, WREG, DBG, PP>), LDS_BYTES, "vq_conv2d_fwd");
+  hipLaunchKernelGGL((conv_igemm_glds_kernel<DT, BC, BP, WC, WP, WREG, DBG, PP>), dim3(p.n_ctiles * p.n_ptiles), dim3(NW * 64), LDS_BYTES, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd(glds)");
+  return VQ_OK;
+}
+template <int DT, int BC, int BP, int WC, int WP>
+static int launch_tap3(ConvParams& p, const ConvPlan&, hipStream_t stream) {
+  constexpr int NW = (BC / WC) * (BP / WP);
+  constexpr int PMAX = (BP + 2 * (BP / 16) + 7) / 8;
+  constexpr size_t LDS_BYTES = (size_t)2 * PMAX * 8 * 64 * sizeof(vq_bf16);
+  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16), "the epilogue transposes the output tile through the same LDS");
+  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
+  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);  p.n_ptiles = (int)vq_ceil_div(p.M, BP);
+  VQ_RESERVE_LDS((conv_igemm_tap3_kernel<DT, BC, BP, WC, WP>), LDS_BYTES, "vq_conv2d_fwd");
+  hipLaunchKernelGGL((conv_igemm_tap3_kernel<DT, BC, BP, WC, WP>), dim3(p.n_ctiles * p.n_ptiles), dim3(NW * 64), LDS_BYTES, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd(tap3)");
+  return VQ_OK;
+}
+template <int DT, int BC, int BP, int WC, int WP, int WA = 0>
+static int launch_tap9(ConvParams& p, const ConvPlan& pl, hipStream_t stream) {
+  constexpr int NW = (BC / WC) * (BP / WP);
+  constexpr int PMAX = ((BP / 16 + 2) * 18 + 7) / 8;
+  constexpr size_t HALO_BYTES = (size_t)PMAX * 8 * 64 * sizeof(vq_bf16), EPI_BYTES = (size_t)BP * BC * sizeof(vq_bf16);
+  // (WA & 4: one halo buffer, or the epilogue's slab where that is larger)
+  constexpr size_t LDS_BYTES = (WA & 4) ? (HALO_BYTES > EPI_BYTES ? HALO_BYTES : EPI_BYTES)
+                                        : ((WA & 2) ? (size_t)32768 : HALO_BYTES) + HALO_BYTES;
+  static_assert(!(WA & 4) || (DT != VQ_F16X2 && 2 * LDS_BYTES <= 160 * 1024), "the one-buffer form: two blocks per CU, no fp32 epilogue slab");
+  VQ_REQUIRE(!(WA & 4) || ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin < ((int64_t)1 << 31) && (int64_t)vq_round_up(p.d.Cout, 32) * p.Kp < ((int64_t)1 << 31)),
+             VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd(tap9): input or packed weights of 2^31 elements or more");
+  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16), "the epilogue transposes the output tile through the same LDS");
+  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
+  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);  p.n_ptiles = p.M / BP;
+  p.pt_tx = p.d.Wo / 16;  p.pt_tpi = p.pt_tx * (p.d.Ho / (BP / 16));
+  VQ_RESERVE_LDS((conv_igemm_tap9_kernel<DT, BC, BP, WC, WP, WA>), LDS_BYTES, "vq_conv2d_fwd");
+  // A single 64-channel chunk (Cin = 64: VGG conv1_2, the 64-channel levels of the reference's own launch line) never touches the
+  // second halo buffer: launched with the first one alone (>= the epilogue's transposition slab), so that the LDS no longer caps
+  // the kernel at two blocks per CU (four fit its 123 VGPRs).  A K = 576 tile is short — 72 MFMAs per wave between a halo DMA that
+  // must land first and an epilogue — and more resident blocks are what covers those two ends: forward +10-18 %, data gradient +5-8 %
+  // (profiles/r6e_c64_onebuf_ab.txt; a deeper weight-fragment ring instead: +-1 %, r6f_tap9_wd_ab.txt).
+  size_t lds_bytes = LDS_BYTES;
+  if (DT != VQ_F16X2 && !(WA & 4) && p.d.Cin == 64 && pl.hint.dbg != 72)        // (the VQ_F16X2 epilogue's fp32 slab is larger; dbg 72 = A/B)
+    lds_bytes = HALO_BYTES > EPI_BYTES ? HALO_BYTES : EPI_BYTES;
+  hipLaunchKernelGGL((conv_igemm_tap9_kernel<DT, BC, BP, WC, WP, WA>), dim3(p.n_ctiles * p.n_ptiles), dim3(NW * 64), lds_bytes, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd(tap9)");
+  return VQ_OK;
+}
+template <int DT, int BC = 256, int S = 3>
+static int launch_p9(ConvParams& p, const ConvPlan&, hipStream_t stream) {
+  constexpr int BP = 256, NW = 8;
+  constexpr int PMAX = (18 * 18 + 7) / 8;
+  constexpr size_t LDS_BYTES = (size_t)2 * BC * 64 * sizeof(vq_bf16) + (size_t)2 * PMAX * 8 * 64 * sizeof(vq_bf16);
+  static_assert(LDS_BYTES >= (size_t)BP * BC * sizeof(vq_bf16) && LDS_BYTES <= 160 * 1024, "epilogue transpose / LDS capacity");
+  static_assert(DT != VQ_F16X2 || LDS_BYTES >= x2_epi_bytes(BC, BP), "the VQ_F16X2 epilogue transposes fp32 slices through the same LDS");
+  if ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin >= ((int64_t)1 << 31)) { vq_set_error("vq_conv2d_fwd(p9): input of 2^31 elements or more"); return VQ_ERR_UNSUPPORTED; }
+  p.n_ctiles = (int)vq_ceil_div(p.d.Cout, BC);  p.n_ptiles = p.M / BP;
+  p.pt_tx = p.d.Wo / 16;  p.pt_tpi = p.pt_tx * (p.d.Ho / 16);
+  VQ_RESERVE_LDS((conv_igemm_p9_kernel<DT, BC, S>), LDS_BYTES, "vq_conv2d_fwd");
+  hipLaunchKernelGGL((conv_igemm_p9_kernel<DT, BC, S>), dim3(p.n_ctiles * p.n_ptiles), dim3(NW * 64), LDS_BYTES, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd(p9)");
+  return VQ_OK;
+}
+// conv_patch_dgrad_kernel (ConvParams already rewritten to the 1x1 form by vq_conv2d_fwd; template parameter KS = K / 16)
+template <int DT>
+static int launch_patch_dgrad(ConvParams& p, hipStream_t stream) {
+  constexpr size_t LDS_BYTES = (size_t)128 * 128 * sizeof(vq_bf16);
+  p.n_ctiles = p.d.Cout / 128;  p.n_ptiles = p.M / 128;
+  // two blocks per CU, every row tile the same number of pixel-tile ranges
+  const int groups = std::max(1, std::min(512 / p.n_ctiles, p.n_ptiles / 4));
+  const int grid = groups * p.n_ctiles;
+  hipLaunchKernelGGL((conv_patch_dgrad_kernel<DT, 2>), dim3(grid), dim3(256), LDS_BYTES, stream, p);
+  VQ_CHECK_LAUNCH("vq_conv2d_fwd(patch dgrad)");
+  return VQ_OK;
+}
+
+// ---- plan -> instantiation.  Every (family, tile, variant) conv_plan can answer has ONE row here; a plan without a row is an error,
+// never another kernel.  Columns: family, BC, BP, WC, WP, v0, v1, v2 (ConvPlan).  tests/test_conv_plan.py reads these rows.
+#define CONV_GENERIC_ROWS(X) X(GENERIC, 128, 128, 64, 64, SPLIT, BK, 0) X(GENERIC, 64, 128, 32, 64, SPLIT, BK, 0) X(GENERIC, 32, 128, 32, 32, SPLIT, BK, 0)
+#define CONV_TILE_ROWS(X)                                                                                        \
+  X(GLDS, 256, 256, 128, 64, 0, 0, 1) X(GLDS, 128, 128, 32, 128, 1, 0, 0) X(GLDS, 128, 128, 64, 64, 0, 0, 0)     \
+  X(GLDS, 64, 128, 32, 64, 1, 0, 0)   X(GLDS, 64, 128, 32, 64, 0, 0, 0)   X(GLDS, 32, 128, 32, 32, 0, 0, 0)      \
+  X(P9, 256, 256, 128, 64, 3, 0, 0)   X(P9, 256, 256, 128, 64, 2, 0, 0)                                          \
+  X(TAP9, 128, 128, 64, 64, 3, 0, 0)  X(TAP9, 64, 128, 64, 32, 3, 0, 0)   X(TAP9, 32, 128, 32, 32, 3, 0, 0)      \
+  X(TAP3, 128, 128, 32, 128, 0, 0, 0) X(TAP3, 64, 128, 32, 64, 0, 0, 0)   X(TAP3, 64, 64, 32, 32, 0, 0, 0)
+#define CONV_TILE_ROWS_NOT_X2(X) X(TAP9, 128, 256, 64, 128, 7, 0, 0)   /* (the VQ_F16X2 epilogue's fp32 slab does not fit) */
+#ifdef VQ_ABLATION_KERNELS
+#define CONV_TILE_ROWS_ABLATE(X)                                                                                 \
+  X(GLDS, 256, 256, 128, 64, 0, 8, 0) X(GLDS, 256, 256, 128, 64, 0, 1, 0) X(GLDS, 256, 256, 128, 64, 0, 0, 0)    \
+  X(GLDS, 128, 128, 64, 64, 0, 8, 0)  X(GLDS, 128, 128, 64, 64, 0, 1, 0)  X(GLDS, 128, 128, 64, 64, 0, 2, 0)     \
+  X(GLDS, 128, 128, 64, 64, 0, 3, 0)  X(GLDS, 128, 128, 64, 64, 0, 4, 0)  X(GLDS, 128, 128, 64, 64, 1, 0, 0)     \
+  X(TAP9, 128, 128, 32, 128, 0, 0, 0) X(TAP9, 128, 128, 64, 64, 0, 0, 0)  X(TAP9, 64, 128, 64, 32, 0, 0, 0)
+#else
+#define CONV_TILE_ROWS_ABLATE(X)
+#endif
+// (GENERIC rows: SPLIT / BK are launch_planned's own — the storage type's)
+#define CONV_INST_GENERIC(DT, BC, BP, WC, WP, A, B, C) launch_conv<DT, A, BC, BP, WC, WP, B>
+#define CONV_INST_GLDS(DT, BC, BP, WC, WP, A, B, C) launch_glds<DT, BC, BP, WC, WP, A, B, C>
+#define CONV_INST_TAP3(DT, BC, BP, WC, WP, A, B, C) launch_tap3<DT, BC, BP, WC, WP>
+#define CONV_INST_TAP9(DT, BC, BP, WC, WP, A, B, C) launch_tap9<DT, BC, BP, WC, WP, A>
+#define CONV_INST_P9(DT, BC, BP, WC, WP, A, B, C) launch_p9<DT, BC, A>
+template <int DT, int SPLIT, int BK>
+static int launch_planned(ConvParams& p, const ConvPlan& pl, hipStream_t stream) {
+#define X(F, BC_, BP_, WC_, WP_, A, B, C)                                                                                              \
+  if (pl.family == CONV_##F && pl.BC == BC_ && pl.BP == BP_ && pl.WC == WC_ && pl.WP == WP_ && pl.v0 == A && pl.v1 == B && pl.v2 == C) \
+    return CONV_INST_##F(DT, BC_, BP_, WC_, WP_, A, B, C)(p, pl, stream);
+  CONV_GENERIC_ROWS(X)
+  if constexpr (DT != VQ_F32) {      // (fp32 storage: conv_igemm_kernel only)
+    CONV_TILE_ROWS(X)
+    CONV_TILE_ROWS_ABLATE(X)
+    if constexpr (DT != VQ_F16X2) { CONV_TILE_ROWS_NOT_X2(X) }
+  }
+#undef X
+  vq_set_error("vq_conv2d_fwd: internal: no instantiation of family %d, tile %d x %d, variant %d / %d / %d", pl.family, pl.BC, pl.BP, pl.v0, pl.v1, pl.v2);
+  return VQ_ERR_UNSUPPORTED;
+}
+
 extern "C" int vq_conv2d_fwd(const VqConvDesc* d0, const void* x, const void* w_packed, const float* bias,
                              const void* residual, const void* relu_mask, void* y, float* gn_partials, int gn_groups,
                              void* stream) {
@@ -2841,18 +2858,16 @@ extern "C" int vq_conv2d_fwd(const VqConvDesc* d0, const void* x, const void* w_
              "vq_conv2d_fwd: channel counts must be positive multiples of 8 (Cin=%d Cout=%d)", d->Cin, d->Cout);
   VQ_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->R > 0 && d->S > 0, VQ_ERR_INVALID,
              "vq_conv2d_fwd: empty tensor");
-  {
-    const int dsh0 = ilog2_exact(d->dil_in), ush0 = ilog2_exact(d->up);
-    VQ_REQUIRE(dsh0 >= 0 && ush0 >= 0 && ush0 <= 1 && d->stride >= 1, VQ_ERR_UNSUPPORTED,
-               "vq_conv2d_fwd: dil_in must be a power of two, up in {1,2} (dil_in=%d up=%d)", d->dil_in, d->up);
-    VQ_REQUIRE(!(dsh0 > 0 && ush0 > 0), VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: dil_in and up cannot be combined");
-  }
+  const int dsh0 = ilog2_exact(d->dil_in), ush0 = ilog2_exact(d->up);
+  VQ_REQUIRE(dsh0 >= 0 && ush0 >= 0 && ush0 <= 1 && d->stride >= 1, VQ_ERR_UNSUPPORTED,
+             "vq_conv2d_fwd: dil_in must be a power of two, up in {1,2} (dil_in=%d up=%d)", d->dil_in, d->up);
+  VQ_REQUIRE(!(dsh0 > 0 && ush0 > 0), VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: dil_in and up cannot be combined");
   VQ_REQUIRE((int64_t)d->N * d->Ho * d->Wo < (1ll << 31) && (int64_t)d->N * d->H * d->W < (1ll << 31), VQ_ERR_UNSUPPORTED,
              "vq_conv2d_fwd: pixel count exceeds int32");
-  VQ_REQUIRE(d->Cin_w <= d->Cin && d->Cout_w <= d->Cout, VQ_ERR_INVALID, "vq_conv2d_fwd: true channels exceed padded");
-  ConvParams p;
+  // (pure host arithmetic on the validated descriptor; the checks below still answer in their old order)
+  const ConvPlan plan = conv_plan(dvirt, ConvCall{residual != nullptr, gn_partials != nullptr, d->gn_bwd != nullptr});
+  ConvParams p = {};
   p.d = *d;
-  p.d2s = 0; p.d2s_c = 0; p.sub = 0; p.pt_tx = 0; p.pt_tpi = 0;
   if (d->subpix) {   // phase-decomposed conv (include/vqhip.h): 4 row blocks, window moved by the phase, depth-to-space store
     VQ_REQUIRE(d->subpix == 2 && d->up == 1 && d->dil_in == 1 && d->Cout % 128 == 0 && d->Cout_w == d->Cout, VQ_ERR_UNSUPPORTED,
                "vq_conv2d_fwd: subpix must be 2 with up = dil_in = 1 and Cout = Cout_w = 4 * (a multiple of 32) (subpix=%d up=%d "
@@ -2860,28 +2875,21 @@ extern "C" int vq_conv2d_fwd(const VqConvDesc* d0, const void* x, const void* w_
     VQ_REQUIRE((int64_t)d->N * d->Ho * d->Wo * 4 < (1ll << 31), VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: pixel count exceeds int32");
     p.d2s = 2; p.d2s_c = d->Cout / 4; p.sub = 1;
   }
-  VqConvDesc pd;
   if (is_patch_dgrad(d)) {   // -> 1x1 conv over the (small) dy image, rows = (tap, ci), depth-to-space store
     VQ_REQUIRE(bias == nullptr && !d->relu, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: patch data-gradient takes no bias / relu");
-    pd = *d;
-    pd.Ho = d->H; pd.Wo = d->W; pd.Cout = d->R * d->S * d->Cout; pd.Cout_w = pd.Cout;
-    pd.R = pd.S = 1; pd.dil_in = 1; pd.pad_t = pd.pad_l = 0;
-    p.d = pd; p.d2s = d->R; p.d2s_c = d->Cout;
-    d = &pd;
+    p.d = patch_dgrad_as_1x1(*d); p.d2s = d->R; p.d2s_c = d->Cout;
+    d = &p.d;
   }
-  const int dsh = ilog2_exact(d->dil_in), ush = ilog2_exact(d->up);
   p.x = x; p.w = (const vq_bf16*)w_packed; p.bias = bias; p.residual = residual; p.relu_mask = relu_mask; p.y = y;
   p.M = d->N * d->Ho * d->Wo;
   p.HoWo = d->Ho * d->Wo;
   p.RS = d->R * d->S;
   p.G8 = d->Cin / 8;
-  p.dsh = dsh; p.ush = ush;
+  p.dsh = ilog2_exact(d->dil_in); p.ush = ilog2_exact(d->up);
   p.Kp = vq_round_up(p.RS * d->Cin, 64);
   p.lo_off = (int64_t)d->Cout * p.Kp;
   p.alpha = d->alpha == 0.f ? 1.f : d->alpha;
   p.alpha_dev = d->alpha_dev;
-  p.gn_part = nullptr; p.gn_G = p.gn_cg = p.gn_bp = p.gn_tiles = p.gn_nw = 0;
-  p.gnb = 0; p.gnb_mean = p.gnb_rstd = p.gnb_gamma = p.gnb_beta = nullptr; p.gnb_part = nullptr; p.gnb_G = p.gnb_silu = p.gnb_rows = 0;
   if (d->gn_bwd) {
     const VqGnBwdFuse* f = d->gn_bwd;
     VQ_REQUIRE(vq_conv2d_gnb_rows(d) > 0, VQ_ERR_UNSUPPORTED,
@@ -2890,52 +2898,41 @@ extern "C" int vq_conv2d_fwd(const VqConvDesc* d0, const void* x, const void* w_
                "vq_conv2d_fwd: incomplete VqGnBwdFuse");
     VQ_REQUIRE(!residual && !relu_mask && !gn_partials && !d->relu, VQ_ERR_UNSUPPORTED,
                "vq_conv2d_fwd: gn_bwd excludes residual / relu_mask / gn_partials / relu on the same call");
-    VQ_REQUIRE(hint_dbg(d) == 0 && (hint_tile(d) & 7) != 4, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: gn_bwd with a kernel_hint that forces an experimental tile");
+    VQ_REQUIRE(plan.hint.dbg == 0 && plan.hint.knob != 4, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: gn_bwd with a kernel_hint that forces an experimental tile");
     p.gnb = 1; p.gnb_mean = f->mean; p.gnb_rstd = f->rstd; p.gnb_gamma = f->gamma; p.gnb_beta = f->beta; p.gnb_part = f->part;
     p.gnb_G = f->groups; p.gnb_silu = f->silu; p.gnb_rows = vq_conv2d_gnb_rows(d);
     p.residual = f->x;                                 // read through the residual operand's request path
   }
-  {
-    const int ws = ilog2_exact(d->Wo), hs = ilog2_exact(d->Ho);
-    p.pix_wsh = (ws >= 0 && hs >= 0) ? ws : -1;
-    p.pix_hwsh = (ws >= 0 && hs >= 0) ? ws + hs : -1;
-  }
-  VQ_REQUIRE(hint_supported(d), VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: kernel_hint %d selects a kernel that only exists in `make ABLATE=1` builds",
+  const int ws = ilog2_exact(d->Wo), hs = ilog2_exact(d->Ho);
+  p.pix_wsh = (ws >= 0 && hs >= 0) ? ws : -1;
+  p.pix_hwsh = (ws >= 0 && hs >= 0) ? ws + hs : -1;
+  VQ_REQUIRE(hint_supported(plan.hint), VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: kernel_hint %d selects a kernel that only exists in `make ABLATE=1` builds",
              d->kernel_hint);
-  {
-    const int g = hint_dbg(d);
-    p.skip_epilogue = (g == 8192 || g == 8201 || g == 8203) ? 1 : g == 8193 ? 2 : g == 8194 ? 3 : g == 8195 ? 4 : g == 8196 ? 5 : 0;
-  }
+  const int g = plan.hint.dbg;
+  p.skip_epilogue = (g == 8192 || g == 8201 || g == 8203) ? 1 : g == 8193 ? 2 : g == 8194 ? 3 : g == 8195 ? 4 : g == 8196 ? 5 : 0;
   p.range_events = (d->dtype == VQ_F16 || d->dtype == VQ_F16X2) ? d->range_events : nullptr;
   if (gn_partials) {
-    VQ_REQUIRE(gn_tile_impl(d, gn_groups) > 0, VQ_ERR_UNSUPPORTED,
+    VQ_REQUIRE(gn_groups_ok(d, gn_groups) && plan.gn_row > 0, VQ_ERR_UNSUPPORTED,
                "vq_conv2d_fwd: this descriptor cannot produce GroupNorm partials (ask vq_conv2d_gn_tile first)");
-    const int bp = gn_kernel_bp(d);
-    p.gn_part = gn_partials; p.gn_G = gn_groups; p.gn_cg = d->Cout / gn_groups; p.gn_bp = bp; p.gn_tiles = (d->Ho * d->Wo) / bp;
-    p.gn_nw = gn_kernel_waves(bp);
+    p.gn_part = gn_partials; p.gn_G = gn_groups; p.gn_cg = d->Cout / gn_groups;
+    p.gn_bp = plan.gn_bp; p.gn_tiles = (d->Ho * d->Wo) / plan.gn_bp; p.gn_nw = plan.gn_nw;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (d->dtype == VQ_BF16 || d->dtype == VQ_F16) {
-    VQ_REQUIRE(d->split == 1, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: 16-bit storage supports split=1 only");
-    const int rc8 = vq_launch_conv_c8(d, x, w_packed, bias, residual, relu_mask, y, p.alpha, p.alpha_dev, s);   // 3-channel image layers
-    if (rc8 <= 0) return rc8;
-    if (patch_dgrad_persistent_ok(p)) return d->dtype == VQ_F16 ? launch_patch_dgrad<VQ_F16>(p, s) : launch_patch_dgrad<VQ_BF16>(p, s);
-    if (d->dtype == VQ_F16) return glds_eligible(d) ? dispatch_glds<VQ_F16>(p, s) : dispatch_tile<VQ_F16, 1, 64>(p, s);
-    if (glds_eligible(d)) return dispatch_glds<VQ_BF16>(p, s);
-    return dispatch_tile<VQ_BF16, 1, 64>(p, s);
-  } else if (d->dtype == VQ_F16X2) {
-    VQ_REQUIRE(d->split == 1 && d->gn_bwd == nullptr, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: VQ_F16X2 storage takes split = 1 and no gn_bwd");
-    if (!gn_partials) {                                // 3-channel image layers (the 8-channel kernel forms no GroupNorm partials)
-      const int rc8 = vq_launch_conv_c8_x2(d, x, w_packed, bias, residual, relu_mask, y, p.alpha, p.alpha_dev, s);
-      if (rc8 <= 0) return rc8;
-    }
-    return glds_eligible(d) ? dispatch_glds<VQ_F16X2>(p, s) : dispatch_tile<VQ_F16X2, 1, 64>(p, s);
-  } else if (d->dtype == VQ_F32) {
-    if (d->split == 1) return dispatch_tile<VQ_F32, 1, 64>(p, s);
-    if (d->split == 3) return dispatch_tile<VQ_F32, 3, 32>(p, s);     // (16-wide chunks measured: 33.8 vs 43.9 img/s, profiles/r4h_*)
-    if (d->split == 6) return dispatch_tile<VQ_F32, 6, 16>(p, s);     // three planes per operand: 16-wide chunks keep the tile in 48 KiB
-    vq_set_error("vq_conv2d_fwd: split must be 1, 3 or 6 (got %d)", d->split);
-    return VQ_ERR_UNSUPPORTED;
+  if (plan.family >= CONV_GLDS) p.wo_shift = ilog2_exact(p.d.Wo);
+  switch (d->dtype) {
+    case VQ_BF16: case VQ_F16:
+      VQ_REQUIRE(d->split == 1, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: 16-bit storage supports split=1 only");
+      if (plan.family == CONV_C8) return vq_launch_conv_c8(d, x, w_packed, bias, residual, relu_mask, y, p.alpha, p.alpha_dev, s);
+      if (plan.family == CONV_PATCH_DGRAD) return d->dtype == VQ_F16 ? launch_patch_dgrad<VQ_F16>(p, s) : launch_patch_dgrad<VQ_BF16>(p, s);
+      return d->dtype == VQ_F16 ? launch_planned<VQ_F16, 1, 64>(p, plan, s) : launch_planned<VQ_BF16, 1, 64>(p, plan, s);
+    case VQ_F16X2:
+      VQ_REQUIRE(d->split == 1 && d->gn_bwd == nullptr, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: VQ_F16X2 storage takes split = 1 and no gn_bwd");
+      if (plan.family == CONV_C8_X2) return vq_launch_conv_c8_x2(d, x, w_packed, bias, residual, relu_mask, y, p.alpha, p.alpha_dev, s);
+      return launch_planned<VQ_F16X2, 1, 64>(p, plan, s);
+    case VQ_F32:
+      VQ_REQUIRE(d->split == 1 || d->split == 3 || d->split == 6, VQ_ERR_UNSUPPORTED, "vq_conv2d_fwd: split must be 1, 3 or 6 (got %d)", d->split);
+      if (d->split == 1) return launch_planned<VQ_F32, 1, 64>(p, plan, s);
+      return d->split == 3 ? launch_planned<VQ_F32, 3, 32>(p, plan, s) : launch_planned<VQ_F32, 6, 16>(p, plan, s);
   }
   vq_set_error("vq_conv2d_fwd: unknown dtype %d", d->dtype);
   return VQ_ERR_INVALID;

@@ -125,12 +125,14 @@ __global__ __launch_bounds__(256) void conv3x3_c8_kernel(const SmallConvParams p
   }
 }
 
+bool vq_conv_c8_shape(const VqConvDesc* d) {
+  return d->subpix == 0 && (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && d->Cin == 8 && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 &&
+         d->up == 1 && d->pad_t == 1 && d->pad_l == 1 && d->Cout <= 128 && d->Ho == d->H && d->Wo == d->W;
+}
 // Returns VQ_OK, or 1 when the shape is not handled here (caller falls through to the generic kernel).
 int vq_launch_conv_c8(const VqConvDesc* d, const void* x, const void* w_packed, const float* bias, const void* residual,
                       const void* relu_mask, void* y, float alpha, const float* alpha_dev, hipStream_t stream) {
-  if (!(d->subpix == 0 && (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && d->Cin == 8 && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 &&
-        d->up == 1 && d->pad_t == 1 && d->pad_l == 1 && residual == nullptr && d->Cout <= 128 && d->Ho == d->H && d->Wo == d->W))
-    return 1;
+  if (!vq_conv_c8_shape(d) || residual != nullptr) return 1;
   SmallConvParams p;
   p.d = *d; p.x = (const vq_bf16*)x; p.w = (const vq_bf16*)w_packed; p.bias = bias; p.relu_mask = (const vq_bf16*)relu_mask;
   p.y = (vq_bf16*)y;

@@ -679,6 +679,7 @@ template <typename... T> __device__ __forceinline__ void vq_tie(T&... regs) { (v
 #endif
 
 // conv_small.hip: dedicated kernels for 8 (padded) input channels; launch_conv_c8 returns 1 if the shape is not its own
+bool vq_conv_c8_shape(const VqConvDesc* d);
 int vq_launch_conv_c8(const VqConvDesc* d, const void* x, const void* w_packed, const float* bias, const void* residual,
                       const void* relu_mask, void* y, float alpha, const float* alpha_dev, hipStream_t stream);
 // the same layers in VQ_F16X2 storage (d = the virtualised descriptor of vq_conv2d_fwd: Cin == 16 virtual channels)
