@@ -473,27 +473,37 @@ size_t vq_wgrad_c8_workspace(const VqConvDesc* d) {
   return (size_t)c8_wgrad_blocks(d) * 96 * (c8_swapped(d) ? d->Cin : d->Cout) * sizeof(float);
 }
 
+// What both launchers derive from the pixel count and the wide side's (virtual) channel count C: the 64-pixel runs, their split over
+// the blocks, and the grid.  Returns the blocks that got runs (the reductions' nblk).
+static int c8_wgrad_grid(const VqConvDesc* d, int C, SmallWgradParams& p, dim3& grid) {
+  p.H = d->H; p.W = d->W; p.C = C;
+  p.M = d->N * d->Ho * d->Wo;
+  p.nruns = p.M / 64;
+  const int nblk = c8_wgrad_blocks(d);
+  p.runs_per_block = (p.nruns + nblk - 1) / nblk;
+  const int used = (p.nruns + p.runs_per_block - 1) / p.runs_per_block;
+  grid = dim3(used, C >= 128 ? C / 128 : 1);
+  return used;
+}
+// (kernel dtype, BT = vq_wgrad_c8_tile(C)) -> instantiation; tests/test_wgrad_plan.py reads these rows
+#define WGRAD_C8_ROWS(X) X(VQ_F16, 128) X(VQ_F16, 64) X(VQ_BF16, 128) X(VQ_BF16, 64)
+static void launch_wgrad_c8_pass(int dtype, const SmallWgradParams& p, dim3 grid, hipStream_t stream) {
+  const int dt = dtype == VQ_F16 ? VQ_F16 : VQ_BF16, bt = vq_wgrad_c8_tile(p.C);
+#define X(DT, BT) if (dt == DT && bt == BT) hipLaunchKernelGGL((wgrad_c8_kernel<DT, BT>), grid, dim3(256), 0, stream, p);
+  WGRAD_C8_ROWS(X)
+#undef X
+}
+
 // *dbias_done = 1 when the bias gradient came out of the same pass (wide tensor == dY)
 int vq_launch_wgrad_c8(const VqConvDesc* d, const void* x, const void* dy, float* dw, float* dbias, int* dbias_done,
                        int accumulate, float alpha, void* workspace, hipStream_t stream) {
   const bool sw = c8_swapped(d);
   SmallWgradParams p;
   p.narrow = (const vq_bf16*)(sw ? dy : x); p.wide = (const vq_bf16*)(sw ? x : dy); p.part = (float*)workspace;
-  p.H = d->H; p.W = d->W; p.C = sw ? d->Cin : d->Cout;
-  p.M = d->N * d->Ho * d->Wo;
   p.nstride = 8; p.noff = 0;
-  p.nruns = p.M / 64;
-  const int nblk = c8_wgrad_blocks(d);
-  p.runs_per_block = (p.nruns + nblk - 1) / nblk;
-  const int used = (p.nruns + p.runs_per_block - 1) / p.runs_per_block;
-  const dim3 grid(used, p.C >= 128 ? p.C / 128 : 1);
-  if (d->dtype == VQ_F16) {
-    if (p.C >= 128) hipLaunchKernelGGL((wgrad_c8_kernel<VQ_F16, 128>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((wgrad_c8_kernel<VQ_F16, 64>), grid, dim3(256), 0, stream, p);
-  } else {
-    if (p.C >= 128) hipLaunchKernelGGL((wgrad_c8_kernel<VQ_BF16, 128>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((wgrad_c8_kernel<VQ_BF16, 64>), grid, dim3(256), 0, stream, p);
-  }
+  dim3 grid;
+  const int used = c8_wgrad_grid(d, sw ? d->Cin : d->Cout, p, grid);
+  launch_wgrad_c8_pass(d->dtype, p, grid, stream);
   VQ_CHECK_LAUNCH("vq_conv2d_wgrad(c8)");
   float* db = sw ? nullptr : dbias;
   *dbias_done = db != nullptr;
@@ -549,20 +559,14 @@ int vq_launch_wgrad_c8_x2(const VqConvDesc* d, const void* x, const void* dy, fl
   const bool sw = c8_x2_swapped(d);
   SmallWgradParams p;
   p.narrow = (const vq_bf16*)(sw ? dy : x); p.wide = (const vq_bf16*)(sw ? x : dy);
-  p.H = d->H; p.W = d->W; p.C = 2 * (sw ? d->Cin : d->Cout);
-  p.M = d->N * d->Ho * d->Wo;
   p.nstride = 16;
-  p.nruns = p.M / 64;
-  const int nblk = c8_wgrad_blocks(d);
-  p.runs_per_block = (p.nruns + nblk - 1) / nblk;
-  const int used = (p.nruns + p.runs_per_block - 1) / p.runs_per_block;
-  const dim3 grid(used, p.C >= 128 ? p.C / 128 : 1);
+  dim3 grid;
+  const int used = c8_wgrad_grid(d, 2 * (sw ? d->Cin : d->Cout), p, grid);
   float* part_h = (float*)workspace;
-  float* part_l = part_h + (size_t)nblk * 96 * p.C;
+  float* part_l = part_h + (size_t)c8_wgrad_blocks(d) * 96 * p.C;
   for (int pl = 0; pl < 2; ++pl) {
     p.noff = pl * 8; p.part = pl ? part_l : part_h;
-    if (p.C >= 128) hipLaunchKernelGGL((wgrad_c8_kernel<VQ_F16, 128>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((wgrad_c8_kernel<VQ_F16, 64>), grid, dim3(256), 0, stream, p);
+    launch_wgrad_c8_pass(VQ_F16, p, grid, stream);
   }
   VQ_CHECK_LAUNCH("vq_conv2d_wgrad(c8, VQ_F16X2)");
   float* db = sw ? nullptr : dbias;

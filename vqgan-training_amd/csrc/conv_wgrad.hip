@@ -1096,6 +1096,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_x2_kernel(const float* __res
     }
   }
 }
+
+// ================================================================================================ host side: plan, launch, queries
 static inline VqConvDesc wg_x2_virtual(const VqConvDesc* d) {
   VqConvDesc v = *d;
   if (v.dtype == VQ_F16X2) { v.dtype = VQ_F16; v.Cin *= 2; v.Cout *= 2; v.Cin_w = v.Cin; v.Cout_w = v.Cout; }
@@ -1107,11 +1109,11 @@ static int ilog2_exact_w(int v) {
   while ((1 << s) < v) ++s;
   return ((1 << s) == v) ? s : -1;
 }
-
-// LDS-DMA kernel preconditions: bf16, single-term MFMA, power-of-two output extent, 64 | M
-static bool wgrad_glds_eligible(const VqConvDesc* d) {
-  return (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && ilog2_exact_w(d->Wo) >= 0 && ilog2_exact_w(d->Ho) >= 0 &&
-         ((int64_t)d->N * d->Ho * d->Wo) % 64 == 0 && d->Cout % 64 == 0 && d->Cin % 64 == 0;
+// log2 of the three-tap kernel's row-segment length: the largest power of two <= 64 dividing Wo
+static int wg_seg_shift(int Wo) {
+  int s = 0;
+  while (s < 6 && Wo % (2 << s) == 0) ++s;
+  return s;
 }
 
 // VqConvDesc.kernel_hint as vq_conv2d_wgrad / vq_conv2d_wgrad_workspace read it (include/vqhip.h; 0 = the plan's own choice, what the
@@ -1119,19 +1121,24 @@ static bool wgrad_glds_eligible(const VqConvDesc* d) {
 // reduction (and, in ABLATE builds, the no-DMA ablation of the one-tap kernel), +16 = the three-tap kernel without the staging
 // stagger, +8 = VQ_F16X2 weight gradients on the virtual 2C x 2C problem (A/B of the native three-product form); bits 16-31 = forced
 // split-K count.  Part of the descriptor: no process-global state.
-static inline int wg_hint_tile(const VqConvDesc* d) { return d->kernel_hint & (64 | 128 | 256); }
-static inline bool wg_hint_no3(const VqConvDesc* d) { return (d->kernel_hint & 4) != 0; }
-static inline bool wg_hint_slow_reduce(const VqConvDesc* d) { return (d->kernel_hint & 1) != 0; }
-static inline bool wg_hint_unstaggered(const VqConvDesc* d) { return (d->kernel_hint & 16) != 0; }
-static inline int wg_hint_split(const VqConvDesc* d) { return (d->kernel_hint >> 16) & 0xffff; }
-static inline bool wg_hint_x2_virtual(const VqConvDesc* d) { return (d->kernel_hint & 8) != 0; }   // +8 = VQ_F16X2 on the virtual problem (rounds 5 form)
-static bool wg_hint_supported(const VqConvDesc* d) { return (d->kernel_hint & 0xffff & ~(1 | 4 | 8 | 16 | 64 | 128 | 256)) == 0; }
+struct WgradHint { int tile; bool slow_reduce, no3, x2_virtual, unstaggered; int split; };
+static inline WgradHint decode_wg_hint(int kernel_hint) {
+  return WgradHint{kernel_hint & (64 | 128 | 256), (kernel_hint & 1) != 0, (kernel_hint & 4) != 0, (kernel_hint & 8) != 0,
+                   (kernel_hint & 16) != 0, (kernel_hint >> 16) & 0xffff};
+}
+static bool wg_hint_supported(int kernel_hint) { return (kernel_hint & 0xffff & ~(1 | 4 | 8 | 16 | 64 | 128 | 256)) == 0; }
 
+// ---- shape predicates: each asked once, by wgrad_plan
+// LDS-DMA kernel preconditions: bf16, single-term MFMA, power-of-two output extent, 64 | M
+static bool wgrad_glds_eligible(const VqConvDesc* d) {
+  return (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && ilog2_exact_w(d->Wo) >= 0 && ilog2_exact_w(d->Ho) >= 0 &&
+         ((int64_t)d->N * d->Ho * d->Wo) % 64 == 0 && d->Cout % 64 == 0 && d->Cin % 64 == 0;
+}
 // conv_wgrad3_kernel: 3x3 / stride 1 / pad 1 (also behind a nearest-2x upsample), 128-multiples of channels, output rows
 // that are a multiple of 4 pixels (<= 96 halo slots)
 // output rows need not be powers of two: a multiple of 4 pixels is enough (crop-invariance batches at every level of the pyramid)
-static bool wgrad3_eligible(const VqConvDesc* d) {
-  return (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && ((int64_t)d->N * d->Ho * d->Wo) % 64 == 0 && !wg_hint_no3(d) && !wg_hint_tile(d) &&
+static bool wgrad3_eligible(const VqConvDesc* d, const WgradHint& h) {
+  return (d->dtype == VQ_BF16 || d->dtype == VQ_F16) && d->split == 1 && ((int64_t)d->N * d->Ho * d->Wo) % 64 == 0 && !h.no3 && !h.tile &&
          d->R == 3 && d->S == 3 && d->stride == 1 && d->dil_in == 1 && (d->up == 1 || d->up == 2) && d->pad_t == 1 &&
          d->pad_l == 1 && d->Ho == d->H * d->up && d->Wo == d->W * d->up && d->Wo % 4 == 0 && d->Cout % 128 == 0 &&
          d->Cin % 128 == 0;
@@ -1147,295 +1154,307 @@ static int wgrad_cus() {
   return 256;
 #endif
 }
-// x3: the native three-product form of the three-tap kernel on a virtualised VQ_F16X2 descriptor (wg_x3): four-wave blocks, two per
-// CU, slabs of REAL channels (a quarter of the virtual problem's)
-static void wgrad_plan(const VqConvDesc* d, int& BT, int& n_ct, int& n_cit, int& nsplit, int& pix_per_split, int* xcd_tiles = nullptr,
-                       bool x3 = false) {
-  if (xcd_tiles) *xcd_tiles = 0;
-  BT = (d->Cout >= 128 && d->Cin >= 128) ? 128 : 64;
-  if (wgrad_glds_eligible(d)) {
+
+// ---- the plan: which kernel computes the partial slabs of a descriptor, over which split-K grid, which reduction sums them, and where
+// the three regions of the workspace lie.  Computed once per call by wgrad_plan; vq_conv2d_wgrad launches from it and
+// vq_conv2d_wgrad_workspace returns its total.  tests/golden/wgrad_plan_table.json records it.
+enum WgradFamily {
+  WG_NONE = 0,               // a storage type / split the entry point refuses (the query still sizes it like WG_GENERIC)
+  WG_C8_X2, WG_C8,           // conv_small.hip: wgrad_c8_kernel twice for VQ_F16X2 storage / once (3-channel image layers); their own reductions
+  WG_TAP3, WG_GLDS,          // the LDS-DMA kernels: conv_wgrad3_kernel (three taps per staged tile), conv_wgrad_glds_kernel (one tap)
+  WG_GENERIC                 // conv_wgrad_kernel<DT, SPLIT, BT, 32, NBUF>: register-staged tiles, every storage type
+};
+enum WgradReduce { WG_RED_OWN = 0, WG_RED_SCALAR, WG_RED_VEC4, WG_RED_VEC9, WG_RED_X2 };   // OWN: the 8-channel families'
+// what the choice depends on beside the descriptor: a bias gradient is wanted; dw is 16-byte aligned (wgrad_reduce9_kernel's stores)
+struct WgradCall { bool bias, dw_aligned; };
+struct WgradPlan {
+  int family;                // WgradFamily
+  int dtype;                 // the storage type the kernel runs in (VQ_F16 for VQ_F16X2 descriptors)
+  int BT, NW, GEN, SEG, STAG, X3, SPLIT, NBUF;   // instantiation (WGRAD_ROWS_*); 8-channel families: BT only
+  int n_ct, n_cit, nsplit, pix_per_split, xcd_tiles;   // WgradParams' fields of the same names
+  int grid_x, grid_y, lds_bytes;
+  int fused_bias;            // the kernel writes bias partials and the reduction sums them; else vq_colsum (8-channel families: their launcher says)
+  int reduce, lpi, red_blocks, bias_blocks;      // WgradReduce, lanes per item, blocks over dW, blocks over the bias partials
+  int slab_real;             // the slabs are indexed by the caller's (real) channel counts, not the virtual ones (X3)
+  int64_t off_bias, off_colsum, total;           // workspace: [ dW partials | bias partials (LDS-DMA kernels) | column-sum scratch ], bytes
+  WgradHint hint;
+};
+enum { WGRAD_PLAN_INTS = 27 };   // family .. total, in declaration order (vq_debug_wgrad_plan)
+
+// d0: the descriptor as the caller wrote it (VQ_F16X2: real channel counts).  Pure host arithmetic (VQ_WGRAD_CUS of ablation builds aside).
+static WgradPlan wgrad_plan(const VqConvDesc& d0, const WgradCall& c) {
+  WgradPlan pl = {};
+  const WgradHint h = pl.hint = decode_wg_hint(d0.kernel_hint);
+  const VqConvDesc dvirt = wg_x2_virtual(&d0);         // VQ_F16X2: the kernels run on the virtual binary16 problem (see wgrad_reduce_x2_kernel)
+  const VqConvDesc* d = &dvirt;
+  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
+  const int RS = d->R * d->S;
+  pl.dtype = d->dtype; pl.SPLIT = d->split; pl.lpi = 1;
+  const bool c8_x2 = vq_wgrad_c8_x2_eligible(&d0);
+  if (c8_x2 || vq_wgrad_c8_eligible(d)) {              // (the second on the VIRTUAL descriptor, as before the plan)
+    pl.family = c8_x2 ? WG_C8_X2 : WG_C8;
+    pl.BT = vq_wgrad_c8_tile(d->Cin > d->Cout ? d->Cin : d->Cout);
+    pl.off_bias = pl.off_colsum = (int64_t)(((c8_x2 ? vq_wgrad_c8_x2_workspace(&d0) : vq_wgrad_c8_workspace(d)) + 255) / 256 * 256);
+    pl.total = pl.off_colsum + (int64_t)vq_colsum_workspace(M, c8_x2 ? d0.Cout : d->Cout);
+    return pl;
+  }
+  const bool three = wgrad3_eligible(d, h), glds = wgrad_glds_eligible(d), lds_dma = three || glds;
+  int BT = (d->Cout >= 128 && d->Cin >= 128) ? 128 : 64;
+  if (glds) {
     // the 256 tile needs a long reduction per block to pay off (measured: wins from ~128k output pixels up)
     // (16-tap descriptors = the transposed form of the Upsample conv, ops.conv_wgrad_raw: 16 tiles per channel-tile pair
     // keep the chip full with long reductions much earlier — measured 997 -> 874 us at 512 channels, 64x64, B = 16)
-    if (d->Cout % 256 == 0 && d->Cin % 256 == 0 &&
-        (int64_t)d->N * d->Ho * d->Wo >= (d->R * d->S >= 16 ? 16384 : 131072)) BT = 256;
+    if (d->Cout % 256 == 0 && d->Cin % 256 == 0 && M >= (RS >= 16 ? 16384 : 131072)) BT = 256;
     else if (d->Cout % 128 == 0 && d->Cin % 128 == 0) BT = 128;
     else BT = 64;
-    if (wg_hint_tile(d) && d->Cout % wg_hint_tile(d) == 0 && d->Cin % wg_hint_tile(d) == 0) BT = wg_hint_tile(d);
+    if (h.tile && d->Cout % h.tile == 0 && d->Cin % h.tile == 0) BT = h.tile;   // (a forced tile that does not divide is ignored)
   }
-  const bool three = wgrad3_eligible(d);
   if (three) BT = 128;
-  n_ct = (int)vq_ceil_div(d->Cout, BT);
-  n_cit = (int)vq_ceil_div(d->Cin, BT);
-  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-  const int tiles = n_ct * n_cit * (three ? 3 : d->R * d->S);
-  // ~1.5 waves of 2 blocks/CU (1 block/CU for the 8-wave 256 tile and the three-tap kernel); more splits only feed the reduce kernel
-  const bool one_per_cu = (BT == 256 || three) && !x3;
+  // VQ_F16X2 in the native three-product form: whatever the three-tap kernel takes on the virtual descriptor (four-wave blocks, two per
+  // CU), and what the one-tap kernel takes on it with tiles of 128 / 256 virtual channels (the 64-wide tile — 16 real channels per wave
+  // and side — keeps the virtual form).  Slabs of REAL channels: a quarter of the virtual problem's.
+  const bool native = d0.dtype == VQ_F16X2 && !h.x2_virtual;
+  const bool x3_tap3 = native && three, x3 = x3_tap3 || (native && glds && BT >= 128);
+  pl.BT = BT; pl.X3 = x3 ? 1 : 0;
+  pl.n_ct = (int)vq_ceil_div(d->Cout, BT);
+  pl.n_cit = (int)vq_ceil_div(d->Cin, BT);
+  const int tiles = pl.n_ct * pl.n_cit * (three ? 3 : RS);
+
+  // -- split-K count.  ~1.5 waves of 2 blocks/CU (1 block/CU for the 8-wave 256 tile and the three-tap kernel); more splits only feed
+  // the reduce kernel.  (The one-tap native form is searched like the virtual problem it replaces: x3_tap3, not x3.)
+  const bool one_per_cu = (BT == 256 || three) && !x3_tap3;
   const int cus = wgrad_cus();
+  const int64_t max_split = vq_ceil_div(M, 512);   // at least 8 chunks of 64 pixels per split
   int64_t want = vq_ceil_div((one_per_cu ? 2 : 3) * cus, tiles);
-  int64_t max_split = vq_ceil_div(M, 512);   // at least 8 chunks of 64 pixels per split
   if (want > max_split) want = max_split;
   if (want < 1) want = 1;
   if (want > 256) want = 256;
-  // the LDS-DMA kernels hand whole splits to XCDs (block % 8): keep all 8 busy and balanced
-  if ((wgrad_glds_eligible(d) || three) && max_split >= 8) want = vq_ceil_div(want, 8) * 8;
-  if ((wgrad_glds_eligible(d) || three) && max_split >= 8) {
+  // three-tap kernel, tiles a multiple of 8: with an XCD owning TILES (all their splits) every split count balances the XCDs; else a
+  // contiguous range of the split-major (split, tile) list
+  const int owner_map = (three && tiles % 8 == 0) ? 1 : 2;
+  int xcd_tiles = 0;
+  if (lds_dma && max_split >= 8) {
+    // The LDS-DMA kernels hand whole splits to XCDs (block % 8): keep all 8 busy and balanced.
     // The grid runs in rounds of `slots` resident blocks (LDS-limited blocks per CU x 256 CUs): pick the split count
     // (multiple of 8) that minimises  kernel time x (rounds * slots / blocks)  +  partial-sum traffic (written once,
     // read once by the reduce).  A plain "blocks >= target" rule left e.g. the 128-channel layers with 528 blocks on
     // 512 slots: a third round for 16 blocks (measured: 712 -> 947 TFLOP/s on that layer).
     const int slots = cus * (one_per_cu ? 1 : (BT == 128 ? 2 : 4));
     const double t_kernel = 2.0 * (double)M * d->Cout * d->Cin * d->R * d->S / 7.0e14;
-    const double t_split = 2.0 * d->R * d->S * d->Cout * d->Cin * 4.0 / 4.0e12 * (x3 ? 0.25 : 1.0);
-    double best = 1e30;
-    for (int64_t ns = 8; ns <= max_split && ns <= 256; ns += 8) {
+    const double t_split = 2.0 * d->R * d->S * d->Cout * d->Cin * 4.0 / 4.0e12 * (x3_tap3 ? 0.25 : 1.0);
+    auto cost = [&](int64_t ns) {
       const int64_t blocks = ns * tiles, rounds = vq_ceil_div(blocks, slots);
-      const double cost = t_kernel * (double)(rounds * slots) / (double)blocks + t_split * (double)ns;
-      if (cost < best) { best = cost; want = ns; }
-    }
-    // three-tap kernel, tiles a multiple of 8: with an XCD owning TILES (all their splits) every split count balances the XCDs
-    if (xcd_tiles) {
-      const int mode = (three && tiles % 8 == 0) ? 1 : 2;
-      if (mode == 2 || tiles % 8 == 0) {
-        for (int64_t ns = 1; ns <= max_split && ns <= 256; ++ns) {
-          const int64_t blocks = ns * tiles, rounds = vq_ceil_div(blocks, slots);
-          const double cost = t_kernel * (double)(rounds * slots) / (double)blocks + t_split * (double)ns;
-          if (cost < best * 0.97) { best = cost; want = ns; *xcd_tiles = mode; }
-        }
-      }
-    }
+      return t_kernel * (double)(rounds * slots) / (double)blocks + t_split * (double)ns;
+    };
+    double best = 1e30;
+    for (int64_t ns = 8; ns <= max_split && ns <= 256; ns += 8)
+      if (const double t = cost(ns); t < best) { best = t; want = ns; }
+    for (int64_t ns = 1; ns <= max_split && ns <= 256; ++ns)     // ... any split count, under a tile-owning map, if it is 3 % better
+      if (const double t = cost(ns); t < best * 0.97) { best = t; want = ns; xcd_tiles = owner_map; }
   }
   // a split count that is not a multiple of 8 (short reductions: fewer than 8 splits possible) under the split-owning map would
   // leave XCDs idle: the range map has no such constraint
-  if (xcd_tiles && *xcd_tiles == 0 && (three || wgrad_glds_eligible(d)) && want % 8 != 0) *xcd_tiles = 2;
-  if (wg_hint_split(d) > 0) {
-    want = wg_hint_split(d) < max_split ? wg_hint_split(d) : max_split;
-    if (xcd_tiles) *xcd_tiles = ((three || wgrad_glds_eligible(d)) && want % 8 != 0) ? ((three && tiles % 8 == 0) ? 1 : 2) : 0;
+  if (xcd_tiles == 0 && lds_dma && want % 8 != 0) xcd_tiles = 2;
+  if (h.split > 0) {                                   // forced: clamped, and the map by a rule of its own
+    want = h.split < max_split ? h.split : max_split;
+    xcd_tiles = (lds_dma && want % 8 != 0) ? owner_map : 0;
   }
-  int64_t pps = vq_ceil_div(vq_ceil_div(M, want), 64) * 64;
-  nsplit = (int)vq_ceil_div(M, pps);
-  pix_per_split = (int)pps;
-}
+  const int64_t pps = vq_ceil_div(vq_ceil_div(M, want), 64) * 64;
+  pl.nsplit = (int)vq_ceil_div(M, pps);
+  pl.pix_per_split = (int)pps;
+  pl.xcd_tiles = xcd_tiles;
 
-static size_t wgrad_part_bytes(const VqConvDesc* d, int nsplit) {
-  return (size_t)nsplit * d->R * d->S * d->Cout * d->Cin * sizeof(float);
-}
-static size_t wgrad_bias_bytes(const VqConvDesc* d, int nsplit) {
-  return ((size_t)nsplit * d->Cout * sizeof(float) + 255) / 256 * 256;
-}
-// VQ_F16X2 weight gradients in the native three-product form: whatever the three-tap kernel takes on the virtual descriptor
-static bool wg_x3(const VqConvDesc* d0, const VqConvDesc* dvirt) {
-  return d0->dtype == VQ_F16X2 && !wg_hint_x2_virtual(d0) && wgrad3_eligible(dvirt);
-}
-// ... and whatever the one-tap LDS-DMA kernel takes on it with tiles of 128 / 256 virtual channels (the plan's BT; the 64-wide tile —
-// 16 real channels per wave and side — keeps the virtual form)
-static bool wg_x3_glds(const VqConvDesc* d0, const VqConvDesc* dvirt, int BT) {
-  return d0->dtype == VQ_F16X2 && !wg_hint_x2_virtual(d0) && !wgrad3_eligible(dvirt) && wgrad_glds_eligible(dvirt) && BT >= 128;
-}
-
-template <int DT, int BT, int NW, int X3 = 0>
-static int launch_wgrad_glds(const WgradParams& p, dim3 grid, hipStream_t s) {
-  constexpr size_t LDS_BYTES = (size_t)2 * 2 * 64 * BT * sizeof(vq_bf16);
-  VQ_RESERVE_LDS((conv_wgrad_glds_kernel<DT, BT, NW, X3>), LDS_BYTES, "vq_conv2d_wgrad");
-  hipLaunchKernelGGL((conv_wgrad_glds_kernel<DT, BT, NW, X3>), grid, dim3(NW * 64), LDS_BYTES, s, p);
-  return VQ_OK;
-}
-
-template <int DT, int GEN, int NW, int SEG, int STAG, int X3 = 0>
-static int launch_wgrad3_form(const WgradParams& p, dim3 grid, hipStream_t s) {
-  constexpr size_t LDS_BYTES = (size_t)2 * (64 + (GEN ? 96 : 72)) * 128 * sizeof(vq_bf16);
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS capacity");
-  VQ_RESERVE_LDS((conv_wgrad3_kernel<DT, GEN, NW, SEG, STAG, X3>), LDS_BYTES, "vq_conv2d_wgrad");
-  hipLaunchKernelGGL((conv_wgrad3_kernel<DT, GEN, NW, SEG, STAG, X3>), grid, dim3(NW * 64), LDS_BYTES, s, p);
-  return VQ_OK;
-}
-template <int DT, int GEN, int NW, int STAG, int X3 = 0>
-static int launch_wgrad3_nw(const WgradParams& p, dim3 grid, hipStream_t s) {
-  if constexpr (GEN) return launch_wgrad3_form<DT, 1, NW, 0, STAG, X3>(p, grid, s);
-  else {
-    if (p.seg_shift == 4) return launch_wgrad3_form<DT, 0, NW, 4, STAG, X3>(p, grid, s);
-    if (p.seg_shift == 5) return launch_wgrad3_form<DT, 0, NW, 5, STAG, X3>(p, grid, s);
-    return launch_wgrad3_form<DT, 0, NW, 6, STAG, X3>(p, grid, s);
+  // -- kernel and grid
+  if (three) {
+    pl.family = WG_TAP3;
+    pl.NW = x3 ? 4 : 8;
+    pl.STAG = (x3 || !h.unstaggered) ? 1 : 0;          // hint +16: every wave stages right after the chunk barrier (rounds 1-2)
+    pl.GEN = (ilog2_exact_w(d->Wo) >= 0 && ilog2_exact_w(d->Ho) >= 0 && d->Wo >= 16) ? 0 : 1;
+    pl.SEG = pl.GEN ? 0 : wg_seg_shift(d->Wo);
+    pl.lds_bytes = 2 * (64 + (pl.GEN ? 96 : 72)) * 128 * (int)sizeof(vq_bf16);
+  } else if (glds) {
+    pl.family = WG_GLDS;
+    pl.NW = BT == 256 ? 8 : 4;
+    pl.lds_bytes = 2 * 2 * 64 * BT * (int)sizeof(vq_bf16);
+  } else {
+    const bool f32 = d->dtype == VQ_F32;
+    const bool known = (d->split == 1 && (f32 || d->dtype == VQ_BF16 || d->dtype == VQ_F16)) || (f32 && (d->split == 3 || d->split == 6));
+    pl.family = known ? WG_GENERIC : WG_NONE;
+    pl.NW = 4;
+    pl.NBUF = (f32 && d->split > 1) ? 1 : 2;
   }
-}
-template <int DT, int GEN>
-static int launch_wgrad3(const WgradParams& p, dim3 grid, hipStream_t s) {
-  // the kernel addresses the input with 32-bit element offsets
-  if ((int64_t)p.d.N * p.d.H * p.d.W * p.d.Cin >= ((int64_t)1 << 31)) { vq_set_error("vq_conv2d_wgrad(three-tap): input of 2^31 elements or more"); return VQ_ERR_UNSUPPORTED; }
-  if constexpr (DT == VQ_F16) {
-    if (p.x3) return launch_wgrad3_nw<DT, GEN, 4, 1, 1>(p, grid, s);    // VQ_F16X2, native three-product form (four waves, staggered staging)
+  if (lds_dma) {                                       // one-dimensional grids, laid out for the XCD map
+    pl.grid_x = (int)(xcd_tiles == 2 ? 8 * vq_ceil_div((int64_t)pl.nsplit * tiles, 8)
+                      : xcd_tiles  ? (int64_t)pl.nsplit * tiles
+                                   : 8 * vq_ceil_div(pl.nsplit, 8) * tiles);
+    pl.grid_y = 1;
+  } else {
+    pl.grid_x = tiles; pl.grid_y = pl.nsplit;
   }
-  // hint +16: every wave stages right after the chunk barrier (rounds 1-2) instead of the staggered form
-  if (!wg_hint_unstaggered(&p.d)) return launch_wgrad3_nw<DT, GEN, 8, 1>(p, grid, s);
-  return launch_wgrad3_nw<DT, GEN, 8, 0>(p, grid, s);
-}
+  pl.fused_bias = (lds_dma && c.bias && (three || RS * pl.n_cit >= BT / 64)) ? 1 : 0;   // FRC blocks per cout tile carry the bias fragments
 
+  // -- reduction.  Outputs are always the caller's true channel counts; the slabs' are real (native form) or virtual.
+  pl.slab_real = x3 ? 1 : 0;
+  const VqConvDesc* ds = x3 ? &d0 : d;
+  const int64_t total = (int64_t)d0.Cout_w * d0.Cin_w * RS;
+  const bool vec = d0.Cin % 4 == 0 && d0.Cin_w % 4 == 0 && !h.slow_reduce;
+  pl.bias_blocks = pl.fused_bias ? (d0.Cout_w + 255) / 256 : 0;
+  int64_t items = total;                               // what the blocks share out: elements, or (tap, co, 4 consecutive ci) items
+  if (d0.dtype == VQ_F16X2 && !x3) {
+    pl.reduce = WG_RED_X2; items = (int64_t)d0.Cout_w * ((d0.Cin_w + 3) / 4) * RS;
+  } else if (RS == 9 && vec && (int64_t)d0.Cout_w * d0.Cin_w >= 512 * 512 && c.dw_aligned) {
+    pl.reduce = WG_RED_VEC9; pl.red_blocks = (int)vq_ceil_div((int64_t)d0.Cout_w * (d0.Cin_w / 4), 256);
+  } else if (vec) {
+    pl.reduce = WG_RED_VEC4; items = total / 4;
+  } else pl.reduce = WG_RED_SCALAR;
+  if (pl.reduce != WG_RED_VEC9) {
+    // lanes per item (X2, VEC4): enough threads for >= 2 blocks per CU (131072), never more lanes than splits
+    while (pl.reduce != WG_RED_SCALAR && pl.lpi < 8 && items * pl.lpi < 131072 && pl.lpi * 2 <= pl.nsplit) pl.lpi *= 2;
+    pl.red_blocks = (int)vq_ceil_div(items * pl.lpi, 256);
+    if (pl.red_blocks > 4096) pl.red_blocks = 4096;
+  }
+
+  // -- workspace (the bias partials are reserved whether or not a bias is fused; the column-sum scratch is sized for the virtual Cout)
+  pl.off_bias = (int64_t)((size_t)pl.nsplit * RS * ds->Cout * ds->Cin * sizeof(float));
+  pl.off_colsum = pl.off_bias + (int64_t)(((size_t)pl.nsplit * ds->Cout * sizeof(float) + 255) / 256 * 256);
+  pl.total = pl.off_colsum + (int64_t)vq_colsum_workspace(M, d->Cout);
+  return pl;
+}
+#ifdef VQ_ABLATION_KERNELS
+// tests only (like vq_debug_conv_plan: not in include/vqhip.h, not in a release library): the plan's integers; flags = WgradCall bits
+// (1 bias gradient wanted, 2 dw 16-byte aligned) -> WGRAD_PLAN_INTS, or -1
+extern "C" int vq_debug_wgrad_plan(const VqConvDesc* d, int flags, long long* out, int n) {
+  if (!d || !out || n < WGRAD_PLAN_INTS) return -1;
+  const WgradPlan pl = wgrad_plan(*d, WgradCall{(flags & 1) != 0, (flags & 2) != 0});
+  const long long v[WGRAD_PLAN_INTS] = {pl.family, pl.dtype, pl.BT, pl.NW, pl.GEN, pl.SEG, pl.STAG, pl.X3, pl.SPLIT, pl.NBUF, pl.n_ct, pl.n_cit,
+                                        pl.nsplit, pl.pix_per_split, pl.xcd_tiles, pl.grid_x, pl.grid_y, pl.lds_bytes, pl.fused_bias, pl.reduce,
+                                        pl.lpi, pl.red_blocks, pl.bias_blocks, pl.slab_real, pl.off_bias, pl.off_colsum, pl.total};
+  memcpy(out, v, sizeof v);
+  return WGRAD_PLAN_INTS;
+}
+#endif
+
+// What Python sizes the workspace by: no call arguments, so the total always holds the column-sum scratch.
 extern "C" size_t vq_conv2d_wgrad_workspace(const VqConvDesc* d0) {
-  if (!d0) return 0;
-  if (vq_wgrad_c8_x2_eligible(d0))
-    return (vq_wgrad_c8_x2_workspace(d0) + 255) / 256 * 256 + vq_colsum_workspace((int64_t)d0->N * d0->Ho * d0->Wo, d0->Cout);
-  const VqConvDesc dvirt = wg_x2_virtual(d0);
-  const VqConvDesc* d = &dvirt;
-  int BT, n_ct, n_cit, nsplit, pps;
-  int xt;
-  bool x3 = wg_x3(d0, d);
-  wgrad_plan(d, BT, n_ct, n_cit, nsplit, pps, &xt, x3);    // the same plan vq_conv2d_wgrad makes (incl. the tile-owning split counts)
-  x3 = x3 || wg_x3_glds(d0, d, BT);
-  // [ dW partials | bias partials (LDS-DMA kernels) | column-sum scratch (other kernels) ]
-  size_t main_bytes = x3 ? wgrad_part_bytes(d0, nsplit) + wgrad_bias_bytes(d0, nsplit)      // (slabs of real channels)
-                         : wgrad_part_bytes(d, nsplit) + wgrad_bias_bytes(d, nsplit);
-  if (vq_wgrad_c8_eligible(d)) main_bytes = (vq_wgrad_c8_workspace(d) + 255) / 256 * 256;
-  return main_bytes + vq_colsum_workspace((int64_t)d->N * d->Ho * d->Wo, d->Cout);
+  return d0 ? (size_t)wgrad_plan(*d0, WgradCall{false, false}).total : 0;
 }
+
+// ---- plan -> instantiation.  Every (family, tile, variant) wgrad_plan can answer for a storage type has ONE row here; a plan without a
+// row is an error, never another kernel.  Columns: family, BT, NW, GEN, SEG, STAG, X3, SPLIT, NBUF (WgradPlan).
+// tests/test_wgrad_plan.py reads these rows.
+// one launcher for every split-K kernel: NW waves per block, the plan's grid and dynamic LDS (none for the register-staged kernel)
+template <void (*KERNEL)(const WgradParams), int NW>
+static int launch_wgrad_kernel(const WgradParams& p, const WgradPlan& pl, hipStream_t s) {
+  static_assert((size_t)2 * (64 + 96) * 128 * sizeof(vq_bf16) <= 160 * 1024, "LDS capacity (three-tap kernel, GEN)");
+  if (pl.lds_bytes) VQ_RESERVE_LDS(KERNEL, pl.lds_bytes, "vq_conv2d_wgrad");
+  hipLaunchKernelGGL(KERNEL, dim3(pl.grid_x, pl.grid_y), dim3(NW * 64), pl.lds_bytes, s, p);
+  return VQ_OK;
+}
+#define WGRAD_TAP3_FORMS(X, NW, STAG, X3) \
+  X(TAP3, 128, NW, 0, 4, STAG, X3, 1, 0) X(TAP3, 128, NW, 0, 5, STAG, X3, 1, 0) X(TAP3, 128, NW, 0, 6, STAG, X3, 1, 0) X(TAP3, 128, NW, 1, 0, STAG, X3, 1, 0)
+#define WGRAD_ROWS_16(X)   /* bf16 and binary16 alike */                                                            \
+  X(GENERIC, 128, 4, 0, 0, 0, 0, 1, 2) X(GENERIC, 64, 4, 0, 0, 0, 0, 1, 2)                                          \
+  X(GLDS, 256, 8, 0, 0, 0, 0, 1, 0)    X(GLDS, 128, 4, 0, 0, 0, 0, 1, 0)   X(GLDS, 64, 4, 0, 0, 0, 0, 1, 0)         \
+  WGRAD_TAP3_FORMS(X, 8, 1, 0) WGRAD_TAP3_FORMS(X, 8, 0, 0)
+#define WGRAD_ROWS_F16_X3(X)   /* VQ_F16X2 operands, native three-product form: binary16 only */                    \
+  X(GLDS, 256, 8, 0, 0, 0, 1, 1, 0)    X(GLDS, 128, 4, 0, 0, 0, 1, 1, 0)   WGRAD_TAP3_FORMS(X, 4, 1, 1)
+#define WGRAD_ROWS_F32(X)                                                                                            \
+  X(GENERIC, 128, 4, 0, 0, 0, 0, 1, 2) X(GENERIC, 64, 4, 0, 0, 0, 0, 1, 2) X(GENERIC, 128, 4, 0, 0, 0, 0, 3, 1)     \
+  X(GENERIC, 64, 4, 0, 0, 0, 0, 3, 1)  X(GENERIC, 128, 4, 0, 0, 0, 0, 6, 1) X(GENERIC, 64, 4, 0, 0, 0, 0, 6, 1)
+#define WG_INST_GENERIC(DT, BT, NW, GEN, SEG, STAG, X3, SPLIT, NBUF) conv_wgrad_kernel<DT, SPLIT, BT, 32, NBUF>
+#define WG_INST_GLDS(DT, BT, NW, GEN, SEG, STAG, X3, SPLIT, NBUF) conv_wgrad_glds_kernel<DT, BT, NW, X3>
+#define WG_INST_TAP3(DT, BT, NW, GEN, SEG, STAG, X3, SPLIT, NBUF) conv_wgrad3_kernel<DT, GEN, NW, SEG, STAG, X3>
+template <int DT>
+static int launch_planned_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s) {
+#define X(F, BT_, NW_, GEN_, SEG_, STAG_, X3_, SPLIT_, NBUF_)                                                                         \
+  if (pl.family == WG_##F && pl.BT == BT_ && pl.NW == NW_ && pl.GEN == GEN_ && pl.SEG == SEG_ && pl.STAG == STAG_ && pl.X3 == X3_ && \
+      pl.SPLIT == SPLIT_ && pl.NBUF == NBUF_)                                                                                          \
+    return launch_wgrad_kernel<WG_INST_##F(DT, BT_, NW_, GEN_, SEG_, STAG_, X3_, SPLIT_, NBUF_), NW_>(p, pl, s);
+  if constexpr (DT == VQ_F32) { WGRAD_ROWS_F32(X) }
+  else {
+    WGRAD_ROWS_16(X)
+    if constexpr (DT == VQ_F16) { WGRAD_ROWS_F16_X3(X) }
+  }
+#undef X
+  vq_set_error("vq_conv2d_wgrad: internal: no instantiation of family %d, tile %d, variant %d / %d / %d / %d / %d / %d", pl.family, pl.BT,
+               pl.NW, pl.GEN, pl.SEG, pl.STAG, pl.X3, pl.SPLIT);
+  return VQ_ERR_UNSUPPORTED;
+}
+// (reduction, lanes per item) -> kernel; wgrad_reduce9_kernel alone takes no tap count
+#define WGRAD_REDUCE_ROWS(X)                                                                                                          \
+  X(SCALAR, 1, wgrad_reduce_kernel)   X(VEC9, 1, wgrad_reduce9_kernel)                                                                \
+  X(VEC4, 1, wgrad_reduce4_kernel<1>) X(VEC4, 2, wgrad_reduce4_kernel<2>) X(VEC4, 4, wgrad_reduce4_kernel<4>) X(VEC4, 8, wgrad_reduce4_kernel<8>) \
+  X(X2, 1, wgrad_reduce_x2_kernel<1>) X(X2, 2, wgrad_reduce_x2_kernel<2>) X(X2, 4, wgrad_reduce_x2_kernel<4>) X(X2, 8, wgrad_reduce_x2_kernel<8>)
+#define WG_TAPS_SCALAR p.RS,
+#define WG_TAPS_VEC4 p.RS,
+#define WG_TAPS_X2 p.RS,
+#define WG_TAPS_VEC9
 
 extern "C" int vq_conv2d_wgrad(const VqConvDesc* d0, const void* x, const void* dy, float* dw, float* dbias, int accumulate,
                                void* workspace, size_t ws_bytes, void* stream) {
   VQ_REQUIRE(d0 && x && dy && dw, VQ_ERR_INVALID, "vq_conv2d_wgrad: null pointer");
-  const bool x2 = d0->dtype == VQ_F16X2;
-  VQ_REQUIRE(!x2 || d0->split == 1, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: VQ_F16X2 storage takes split = 1");
-  const VqConvDesc dvirt = wg_x2_virtual(d0);          // VQ_F16X2: the kernels run on the virtual binary16 problem (see wgrad_reduce_x2_kernel)
+  VQ_REQUIRE(d0->dtype != VQ_F16X2 || d0->split == 1, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: VQ_F16X2 storage takes split = 1");
+  const VqConvDesc dvirt = wg_x2_virtual(d0);
   const VqConvDesc* d = &dvirt;
   VQ_REQUIRE(d->Cin % 8 == 0 && d->Cout % 8 == 0, VQ_ERR_INVALID, "vq_conv2d_wgrad: channels must be multiples of 8");
   const int dsh = ilog2_exact_w(d->dil_in), ush = ilog2_exact_w(d->up);
   VQ_REQUIRE(dsh >= 0 && ush >= 0 && ush <= 1, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: bad dil_in/up");
   VQ_REQUIRE(d->subpix == 0, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: sub-pixel descriptors are forward-only");
-  VQ_REQUIRE(wg_hint_supported(d), VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: unknown kernel_hint bits (%d)", d->kernel_hint);
-  VQ_REQUIRE((int64_t)d->N * d->Ho * d->Wo < (1ll << 31) - 4096, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: pixel count exceeds int32");
-  const size_t need = vq_conv2d_wgrad_workspace(d0);
-  VQ_REQUIRE(workspace && ws_bytes >= need, VQ_ERR_WORKSPACE, "vq_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
+  VQ_REQUIRE(wg_hint_supported(d->kernel_hint), VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: unknown kernel_hint bits (%d)", d->kernel_hint);
+  const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
+  VQ_REQUIRE(M < (1ll << 31) - 4096, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: pixel count exceeds int32");
+  const WgradPlan pl = wgrad_plan(*d0, WgradCall{dbias != nullptr, ((uintptr_t)dw & 15) == 0});
+  VQ_REQUIRE(workspace && ws_bytes >= (size_t)pl.total, VQ_ERR_WORKSPACE, "vq_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes,
+             (size_t)pl.total);
   const float alpha = d->alpha == 0.f ? 1.f : d->alpha;
-  if (vq_wgrad_c8_x2_eligible(d0)) {   // the 3-channel image layers in VQ_F16X2 storage: two passes of the one-pass kernel (conv_small.hip)
-    int bias_done = 0;
-    int rc = vq_launch_wgrad_c8_x2(d0, x, dy, dw, dbias, &bias_done, accumulate, alpha, workspace, (hipStream_t)stream);
-    if (rc) return rc;
-    if (dbias && !bias_done) {
-      const int64_t pixels = (int64_t)d0->N * d0->Ho * d0->Wo;
-      void* cws = (char*)workspace + (vq_wgrad_c8_x2_workspace(d0) + 255) / 256 * 256;
-      return vq_colsum(dy, pixels, d0->Cout, d0->dtype, dbias, d0->Cout_w, accumulate, alpha, nullptr, cws,
-                       vq_colsum_workspace(pixels, d0->Cout), stream);
-    }
-    return VQ_OK;
-  }
-  if (vq_wgrad_c8_eligible(d)) {   // 3-channel image layers: one pass over dY for all 9 taps (conv_small.hip)
-    VQ_REQUIRE(d->alpha_dev == nullptr, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: the 8-channel kernels take a host alpha only");
-    int bias_done = 0;
-    int rc = vq_launch_wgrad_c8(d, x, dy, dw, dbias, &bias_done, accumulate, alpha, workspace, (hipStream_t)stream);
-    if (rc) return rc;
-    if (dbias && !bias_done) {
-      const int64_t pixels = (int64_t)d->N * d->Ho * d->Wo;
-      void* cws = (char*)workspace + (vq_wgrad_c8_workspace(d) + 255) / 256 * 256;
-      return vq_colsum(dy, pixels, d->Cout, d->dtype, dbias, d->Cout_w, accumulate, alpha, nullptr, cws,
-                       vq_colsum_workspace(pixels, d->Cout), stream);
-    }
-    return VQ_OK;
-  }
-  WgradParams p;
-  p.d = *d; p.x = x; p.dy = dy; p.part = (float*)workspace;
-  p.M = d->N * d->Ho * d->Wo; p.HoWo = d->Ho * d->Wo; p.RS = d->R * d->S;
-  p.dsh = dsh; p.ush = ush;
-  int BT, nsplit;
-  bool x3 = wg_x3(d0, d);
-  wgrad_plan(d, BT, p.n_ct, p.n_cit, nsplit, p.pix_per_split, &p.xcd_tiles, x3);
-  x3 = x3 || wg_x3_glds(d0, d, BT);
-  p.x3 = x3 ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(p.n_ct * p.n_cit * p.RS, nsplit);
-  p.wo_shift = ilog2_exact_w(d->Wo); p.ho_shift = ilog2_exact_w(d->Ho);
-  const bool glds_ok = wgrad_glds_eligible(d) || wgrad3_eligible(d);
-  p.seg_shift = 0;
-  while (p.seg_shift < 6 && d->Wo % (2 << p.seg_shift) == 0) ++p.seg_shift;
-  const VqConvDesc* ds = x3 ? d0 : d;                  // the descriptor whose channel counts index the slabs and the split reduction
-  float* bias_part = (float*)((char*)workspace + wgrad_part_bytes(ds, nsplit));
-  void* colsum_ws = (char*)bias_part + wgrad_bias_bytes(ds, nsplit);
-  p.bias_part = (glds_ok && dbias && (wgrad3_eligible(d) || p.RS * p.n_cit >= BT / 64)) ? bias_part : nullptr;   // FRC blocks per cout tile carry the bias fragments
-#define VQ_WG(DTv, SPv, BTv, NB) \
-  hipLaunchKernelGGL((conv_wgrad_kernel<DTv, SPv, BTv, 32, NB>), grid, dim3(256), 0, s, p)
-  p.nsplit = nsplit;
-#ifdef VQ_ABLATION_KERNELS
-  p.dbg = wg_hint_slow_reduce(d) ? 1 : 0;
-#else
-  p.dbg = 0;
-#endif
-  if (glds_ok) {
-    int rc = VQ_OK;
-    const bool three = wgrad3_eligible(d);
-    const dim3 grid1(p.xcd_tiles == 2 ? 8u * (unsigned)vq_ceil_div((int64_t)nsplit * (p.n_ct * p.n_cit * (three ? 3 : p.RS)), 8)
-                     : p.xcd_tiles ? (unsigned)nsplit * (unsigned)(p.n_ct * p.n_cit * 3)
-                                 : 8u * (unsigned)vq_ceil_div(nsplit, 8) * (unsigned)(p.n_ct * p.n_cit * (three ? 3 : p.RS)));
-    const bool pow2 = p.wo_shift >= 0 && p.ho_shift >= 0 && d->Wo >= 16;
-    if (d->dtype == VQ_F16) {
-      if (three) rc = pow2 ? launch_wgrad3<VQ_F16, 0>(p, grid1, s) : launch_wgrad3<VQ_F16, 1>(p, grid1, s);
-      else if (BT == 256) rc = p.x3 ? launch_wgrad_glds<VQ_F16, 256, 8, 1>(p, grid1, s) : launch_wgrad_glds<VQ_F16, 256, 8>(p, grid1, s);
-      else if (BT == 128) rc = p.x3 ? launch_wgrad_glds<VQ_F16, 128, 4, 1>(p, grid1, s) : launch_wgrad_glds<VQ_F16, 128, 4>(p, grid1, s);
-      else rc = launch_wgrad_glds<VQ_F16, 64, 4>(p, grid1, s);
-    } else {
-      if (three) rc = pow2 ? launch_wgrad3<VQ_BF16, 0>(p, grid1, s) : launch_wgrad3<VQ_BF16, 1>(p, grid1, s);
-      else if (BT == 256) rc = launch_wgrad_glds<VQ_BF16, 256, 8>(p, grid1, s);
-      else if (BT == 128) rc = launch_wgrad_glds<VQ_BF16, 128, 4>(p, grid1, s);
-      else rc = launch_wgrad_glds<VQ_BF16, 64, 4>(p, grid1, s);
-    }
+  bool bias_fused = pl.fused_bias != 0;
+  const VqConvDesc* dcs = d0;                          // whose channel counts and storage type the column sum reads
+  if (pl.family == WG_C8 || pl.family == WG_C8_X2) {   // the 3-channel image layers: one pass over dY for all 9 taps (conv_small.hip)
+    VQ_REQUIRE(pl.family == WG_C8_X2 || d->alpha_dev == nullptr, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: the 8-channel kernels take a host alpha only");
+    int bias_done = 0;
+    const int rc = pl.family == WG_C8_X2 ? vq_launch_wgrad_c8_x2(d0, x, dy, dw, dbias, &bias_done, accumulate, alpha, workspace, s)
+                                         : vq_launch_wgrad_c8(d, x, dy, dw, dbias, &bias_done, accumulate, alpha, workspace, s);
     if (rc) return rc;
-  } else if (d->dtype == VQ_BF16 && d->split == 1) {
-    if (BT == 128) VQ_WG(VQ_BF16, 1, 128, 2); else VQ_WG(VQ_BF16, 1, 64, 2);
-  } else if (d->dtype == VQ_F16 && d->split == 1) {
-    if (BT == 128) VQ_WG(VQ_F16, 1, 128, 2); else VQ_WG(VQ_F16, 1, 64, 2);
-  } else if (d->dtype == VQ_F32 && d->split == 1) {
-    if (BT == 128) VQ_WG(VQ_F32, 1, 128, 2); else VQ_WG(VQ_F32, 1, 64, 2);
-  } else if (d->dtype == VQ_F32 && d->split == 3) {
-    if (BT == 128) VQ_WG(VQ_F32, 3, 128, 1); else VQ_WG(VQ_F32, 3, 64, 1);
-  } else if (d->dtype == VQ_F32 && d->split == 6) {
-    if (BT == 128) VQ_WG(VQ_F32, 6, 128, 1); else VQ_WG(VQ_F32, 6, 64, 1);
+    bias_fused = bias_done != 0;
+    if (pl.family == WG_C8) dcs = d;                   // (the virtual descriptor it was found eligible on)
   } else {
-    vq_set_error("vq_conv2d_wgrad: unsupported dtype/split combination (%d/%d)", d->dtype, d->split);
-    return VQ_ERR_UNSUPPORTED;
+    VQ_REQUIRE(pl.family != WG_NONE, VQ_ERR_UNSUPPORTED, "vq_conv2d_wgrad: unsupported dtype/split combination (%d/%d)", d->dtype, d->split);
+    // the three-tap kernel addresses the input with 32-bit element offsets
+    VQ_REQUIRE(pl.family != WG_TAP3 || (int64_t)d->N * d->H * d->W * d->Cin < ((int64_t)1 << 31), VQ_ERR_UNSUPPORTED,
+               "vq_conv2d_wgrad(three-tap): input of 2^31 elements or more");
+    float* bias_part = (float*)((char*)workspace + pl.off_bias);
+    WgradParams p = {};
+    p.d = *d; p.x = x; p.dy = dy; p.part = (float*)workspace;
+    p.bias_part = bias_fused ? bias_part : nullptr;
+#ifdef VQ_ABLATION_KERNELS
+    p.dbg = pl.hint.slow_reduce ? 1 : 0;
+#endif
+    p.M = (int)M; p.HoWo = d->Ho * d->Wo; p.RS = d->R * d->S;
+    p.n_ct = pl.n_ct; p.n_cit = pl.n_cit;
+    p.dsh = dsh; p.ush = ush;
+    p.pix_per_split = pl.pix_per_split; p.nsplit = pl.nsplit; p.xcd_tiles = pl.xcd_tiles;
+    p.wo_shift = ilog2_exact_w(d->Wo); p.ho_shift = ilog2_exact_w(d->Ho);
+    p.seg_shift = wg_seg_shift(d->Wo);
+    p.x3 = pl.X3;
+    const int rc = d->dtype == VQ_F32   ? launch_planned_wgrad<VQ_F32>(p, pl, s)
+                   : d->dtype == VQ_F16 ? launch_planned_wgrad<VQ_F16>(p, pl, s)
+                                        : launch_planned_wgrad<VQ_BF16>(p, pl, s);
+    if (rc) return rc;
+    VQ_CHECK_LAUNCH("vq_conv2d_wgrad");
+    // the split reduction sums the slabs in their fixed order and scatters into the OIHW gradient (and the bias partials into dbias)
+    const dim3 rgrid(pl.red_blocks + pl.bias_blocks);
+    const VqConvDesc* ds = pl.slab_real ? d0 : d;
+#define X(KIND, LPI, KERNEL)                                                                                                           \
+  if (pl.reduce == WG_RED_##KIND && pl.lpi == LPI)                                                                                     \
+    hipLaunchKernelGGL(KERNEL, rgrid, dim3(256), 0, s, (const float*)workspace, pl.nsplit, WG_TAPS_##KIND ds->Cout, ds->Cin, d0->Cout_w, \
+                       d0->Cin_w, accumulate, dw, (const float*)bias_part, dbias, pl.red_blocks, alpha, d->alpha_dev);
+    WGRAD_REDUCE_ROWS(X)
+#undef X
+    VQ_CHECK_LAUNCH("vq_conv2d_wgrad(reduce)");
   }
-#undef VQ_WG
-  VQ_CHECK_LAUNCH("vq_conv2d_wgrad");
-  d = ds;                                              // (from here on: the reduction's view — real channels for the native form)
-  const int64_t total = (int64_t)d->Cout_w * d->Cin_w * p.RS;
-  int blocks = (int)vq_ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
-  const int bias_blocks = (dbias && p.bias_part) ? (d->Cout_w + 255) / 256 : 0;
-  if (x2 && !x3) {
-    const int64_t items = (int64_t)d0->Cout_w * ((d0->Cin_w + 3) / 4) * p.RS;
-    int lpi = 1;
-    while (lpi < 8 && items * lpi < 131072 && lpi * 2 <= nsplit) lpi *= 2;
-    blocks = (int)vq_ceil_div(items * lpi, 256);
-    if (blocks > 4096) blocks = 4096;
-    const int bb = (dbias && p.bias_part) ? (d0->Cout_w + 255) / 256 : 0;
-#define VQ_RX(L) hipLaunchKernelGGL(wgrad_reduce_x2_kernel<L>, dim3(blocks + bb), dim3(256), 0, s, (const float*)workspace, nsplit, p.RS, \
-                       d->Cout, d->Cin, d0->Cout_w, d0->Cin_w, accumulate, dw, (const float*)bias_part, dbias, blocks, alpha, d->alpha_dev)
-    if (lpi == 8) VQ_RX(8); else if (lpi == 4) VQ_RX(4); else if (lpi == 2) VQ_RX(2); else VQ_RX(1);
-#undef VQ_RX
-  } else
-  if (p.RS == 9 && d->Cin % 4 == 0 && d->Cin_w % 4 == 0 && (int64_t)d->Cout_w * d->Cin_w >= 512 * 512 && !wg_hint_slow_reduce(d) &&
-      ((uintptr_t)dw & 15) == 0) {
-    blocks = (int)vq_ceil_div((int64_t)d->Cout_w * (d->Cin_w / 4), 256);
-    hipLaunchKernelGGL(wgrad_reduce9_kernel, dim3(blocks + bias_blocks), dim3(256), 0, s, (const float*)workspace, nsplit, d->Cout,
-                       d->Cin, d->Cout_w, d->Cin_w, accumulate, dw, (const float*)bias_part, dbias, blocks, alpha, d->alpha_dev);
-  } else if (d->Cin % 4 == 0 && d->Cin_w % 4 == 0 && !wg_hint_slow_reduce(d)) {
-    // lanes per item: enough threads for >= 2 blocks per CU (131072), never more lanes than splits
-    const int64_t items = total / 4;
-    int lpi = 1;
-    while (lpi < 8 && items * lpi < 131072 && lpi * 2 <= nsplit) lpi *= 2;
-    blocks = (int)vq_ceil_div(items * lpi, 256);
-    if (blocks > 4096) blocks = 4096;
-#define VQ_R4(L) hipLaunchKernelGGL(wgrad_reduce4_kernel<L>, dim3(blocks + bias_blocks), dim3(256), 0, s, (const float*)workspace, nsplit, p.RS, \
-                       d->Cout, d->Cin, d->Cout_w, d->Cin_w, accumulate, dw, (const float*)bias_part, dbias, blocks, alpha, d->alpha_dev)
-    if (lpi == 8) VQ_R4(8); else if (lpi == 4) VQ_R4(4); else if (lpi == 2) VQ_R4(2); else VQ_R4(1);
-#undef VQ_R4
-  } else
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + bias_blocks), dim3(256), 0, s, (const float*)workspace, nsplit, p.RS,
-                     d->Cout, d->Cin, d->Cout_w, d->Cin_w, accumulate, dw, (const float*)bias_part, dbias, blocks, alpha, d->alpha_dev);
-  VQ_CHECK_LAUNCH("vq_conv2d_wgrad(reduce)");
-  if (dbias) {
-    if (p.bias_part) {
-    } else {
-      const int64_t pixels = (int64_t)d->N * d->Ho * d->Wo;
-      int rc = vq_colsum(dy, pixels, d0->Cout, d0->dtype, dbias, d0->Cout_w, accumulate, alpha, d->alpha_dev, colsum_ws,
-                         vq_colsum_workspace(pixels, d0->Cout), stream);
-      if (rc) return rc;
-    }
-  }
+  if (dbias && !bias_fused)
+    return vq_colsum(dy, M, dcs->Cout, dcs->dtype, dbias, dcs->Cout_w, accumulate, alpha, d->alpha_dev, (char*)workspace + pl.off_colsum,
+                     vq_colsum_workspace(M, dcs->Cout), stream);
   return VQ_OK;
 }

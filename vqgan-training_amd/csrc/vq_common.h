@@ -695,6 +695,8 @@ bool vq_wgrad_c8_x2_eligible(const VqConvDesc* d);
 size_t vq_wgrad_c8_x2_workspace(const VqConvDesc* d);
 int vq_launch_wgrad_c8_x2(const VqConvDesc* d, const void* x, const void* dy, float* dw, float* dbias, int* dbias_done, int accumulate, float alpha,
                           void* workspace, hipStream_t stream);
+// channel tile (wgrad_c8_kernel's BT) of both, by the wide side's virtual channel count
+static inline int vq_wgrad_c8_tile(int wide) { return wide >= 128 ? 128 : 64; }
 
 // compile-time unrolled loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
 #include <utility>
