@@ -382,6 +382,8 @@ int vq_scale(const float* x, float alpha, const float* alpha_dev, int64_t n, flo
  * VQ codebook nearest lookup (NOT in the reference — SURVEY F1; oracle/vq_oracle.py defines it)
  *   d_ij = |z_i|^2 - 2 z_i.e_j + |e_j|^2  evaluated in fp32 with the fixed sequential order
  *   documented in oracle/vq_oracle.py; idx_i = argmin_j d_ij, lowest index wins ties.
+ * dim: 4, or any multiple of 8 from 8 to 256 (VQ_ERR_UNSUPPORTED otherwise); bit-exact against the oracle at every one of them.
+ * workspace >= vq_vq_workspace(n_tokens, n_codes) bytes: the size does not depend on dim.  zq and min_dist may be NULL.
  */
 size_t vq_vq_workspace(int64_t n_tokens, int n_codes);
 int vq_vq_nearest_fwd(const float* z, const float* codebook, int64_t n_tokens, int n_codes, int dim,

@@ -281,6 +281,251 @@ __global__ __launch_bounds__(256) void vq_nearest_mfma_kernel(const float* __res
   }
 }
 
+// The end of a split as in vq_nearest_mfma_kernel (which keeps its own copy, so that its instruction stream stays the measured one):
+// the halving exchange over the 32 lanes that hold one token's codes, smaller d first, the lower index on ties.
+__device__ __forceinline__ void vq_mfma_split_store(const float (&best)[16], const int (&besti)[16], int fr, int fh, int64_t tok0,
+                                                    int64_t n_tokens, float* __restrict__ pmin, int* __restrict__ pidx) {
+  float b[16];
+  int bi[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { b[e] = best[e]; bi[e] = besti[e] + fr; }
+#pragma unroll
+  for (int lvl = 0; lvl < 4; ++lvl) {
+    const int m = 16 >> lvl, n = 8 >> lvl;          // lane distance, elements kept
+    const bool up = (fr & m) != 0;
+#pragma unroll
+    for (int e = 0; e < n; ++e) {
+      const float keep = up ? b[e + n] : b[e], send = up ? b[e] : b[e + n];
+      const int keepi = up ? bi[e + n] : bi[e], sendi = up ? bi[e] : bi[e + n];
+      const float ob = __shfl_xor(send, m);
+      const int oi = __shfl_xor(sendi, m);
+      const bool take = ob < keep || (ob == keep && oi < keepi);
+      b[e] = take ? ob : keep;
+      bi[e] = take ? oi : keepi;
+    }
+  }
+  {
+    const float ob = __shfl_xor(b[0], 1);
+    const int oi = __shfl_xor(bi[0], 1);
+    if (ob < b[0] || (ob == b[0] && oi < bi[0])) { b[0] = ob; bi[0] = oi; }
+  }
+  // the element a lane ends with: bit 3 <- lane bit 4, bit 2 <- bit 3, bit 1 <- bit 2, bit 0 <- bit 1
+  const int e_mine = fr >> 1;
+  const int64_t t = tok0 + (e_mine & 3) + 8 * (e_mine >> 2) + 4 * fh;
+  if ((fr & 1) == 0 && t < n_tokens) {
+    pmin[(int64_t)blockIdx.y * n_tokens + t] = b[0];
+    pidx[(int64_t)blockIdx.y * n_tokens + t] = bi[0];
+  }
+}
+
+// The WIDE form of the same search: every code dimension D that is a multiple of 8 up to 256 and has no narrow instantiation (24, 40,
+// 48, 56, 72 ... 256).  vq_nearest_mfma_kernel<D> keeps A, two whole B rows and a 64-code tile pair resident, which at D = 256 would be
+// over 384 registers of operands and 256 KiB of LDS; here only the A operand is resident (D / 2 registers: the token's components of
+// this lane's parity) and B is streamed from LDS in k-chunks of 32 (16 registers per lane, two buffers: the next chunk's 16-byte reads
+// are in flight under this chunk's 16 MFMAs; the last chunk may be short, in whole groups of 8 k).  One token / code pair's dot is
+// still ONE chain of D / 2 MFMAs onto ONE accumulator, k ascending — the chunks only cut the instruction stream, never the chain —
+// so the bits are the oracle's.  D is a template parameter: with `dim` as a kernel argument the chunk and remainder guards became
+// scalar branches, one basic block per four MFMAs, and hipcc drained the LDS queue (lgkmcnt(0)) in front of every read: the chain
+// waited for each read in turn (8192 x 16384 x 256: 783 us, against 670 us in this form).  Two waves per SIMD are part of the design:
+// one wave's single dependent chain does not hold the MFMA rate (the same kernel bounded to one wave per SIMD, reads a whole chunk
+// ahead: 873 us; profiles/vq_wide_dims.txt).  Code tiles of 32 (one MFMA block per wave and
+// tile), two LDS buffers in the narrow kernel's [code][parity][D / 2] (+ 4 floats) image, the next tile staged through
+// ceil(D / 32) float4 registers per thread: thread = (code tid >> 3, pieces tid & 7, + 8, ...).  Rows past the split's end are zeros
+// with |e|^2 = +inf, token rows past n_tokens are zeros and store nothing; scan, split merge and grid are the narrow kernel's.
+// hipcc's figures for gfx950 (-Rpass-analysis=kernel-resource-usage), __launch_bounds__(256, 2); no AGPRs, no scratch at any D;
+// LDS is dynamic, 8 * 32 * (D + 4) + 256 bytes (D = 256 alone passes 64 KiB and takes the opt-in; two blocks still fit a CU):
+//     D    VGPRs  waves / SIMD  LDS           D    VGPRs  waves / SIMD  LDS
+//     24    103       4          7,424 B      128   168       3         34,048 B
+//     56    124       4         15,616 B      136   175       2         36,096 B
+//     72    135       3         19,712 B      200   216       2         52,480 B
+//     96    148       3         25,856 B      256   247       2         66,816 B
+static constexpr int VQ_WIDE_CT = 32;
+static constexpr size_t vq_wide_lds_bytes(int dim) { return ((size_t)2 * VQ_WIDE_CT * (dim + 4) + 2 * VQ_WIDE_CT) * sizeof(float); }
+// (the dynamic LDS array is declared once, outside the template: the host emulation gives every declaration its own 160 KiB of
+// thread-local storage, which 28 instantiations would have multiplied)
+__device__ __forceinline__ float* vq_wide_lds() {
+  VQ_DYN_LDS(float, lds);
+  return lds;
+}
+template <int D>
+__global__ __launch_bounds__(256, 2) void vq_nearest_wide_kernel(const float* __restrict__ z, const float* __restrict__ cb,
+                                                               const float* __restrict__ ee_all, int64_t n_tokens, int n_codes,
+                                                               int codes_per_split, float* __restrict__ pmin, int* __restrict__ pidx) {
+  constexpr int dim = D, NCH = (D + 31) / 32;         // k-chunks of 32, the last one may be short (whole groups of 8)
+  constexpr int CT = VQ_WIDE_CT, KSMAX = 16 * NCH;
+  static_assert(CT == 32 && D % 8 == 0 && D >= 8 && D <= 256, "one 32-code MFMA block per tile; 8 threads stage a code");
+  float* const lds = vq_wide_lds();                   // tile[2][CT * RS] ([code][parity][KS] + pad), then tee[2][CT]; first, 64 token rows
+  static_assert(2 * CT * 4 + 2 * CT >= 64, "64 token rows of dim + 1 floats fit in the tile buffers");
+  constexpr int KS = dim >> 1, RS = dim + 4, NQ = dim >> 2;   // RS / 4 is odd: 16 lanes' 16-byte reads cover the 64 banks once
+  float* const tee = lds + 2 * CT * RS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 31, fh = lane >> 5;
+  const int64_t tok0 = (int64_t)blockIdx.x * 128 + wave * 32;
+  const int64_t tok = tok0 + fr;
+  const bool live = tok < n_tokens;
+  // A operand + the token's |z|^2 (full chain, k ascending: both halves of the wave compute it).  The block's 128 token rows come in
+  // through the (still unused) tile buffers, 64 rows at a time: one wave instruction copies 256 contiguous bytes of a row, and a
+  // lane then walks its own row in LDS (row stride dim + 1, odd: the 32 rows of a wave sit in 32 different banks).  Lanes reading
+  // their rows straight from global memory touch 32 cache lines per instruction for 4 bytes each; at 8192 x 1024 x 256 that
+  // prologue was most of the kernel's time.
+  float az[KSMAX];
+  float zz = 0.f;
+#pragma unroll
+  for (int sidx = 0; sidx < KSMAX; ++sidx) az[sidx] = 0.f;
+  {
+    constexpr int RZ = dim + 1;
+    const int64_t btok0 = (int64_t)blockIdx.x * 128;
+#pragma nounroll
+    for (int half = 0; half < 2; ++half) {
+      if (half) __syncthreads();                       // (the first 64 rows have been read)
+#pragma unroll
+      for (int kc = 0; kc < (NCH + 1) / 2; ++kc) {       // rows wave, wave + 4, ...: 16 loads in flight per lane
+        const int k = kc * 64 + lane;
+        if (kc * 64 < dim) {
+          float v[16];
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr) {
+            const int64_t t = btok0 + half * 64 + wave + 4 * rr;
+            v[rr] = (t < n_tokens && k < dim) ? z[t * dim + k] : 0.f;
+          }
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr)
+            if (k < dim) lds[(wave + 4 * rr) * RZ + k] = v[rr];
+        }
+      }
+      __syncthreads();
+      if ((wave >> 1) == half) {
+        const float* zr = lds + ((wave & 1) * 32 + fr) * RZ;
+#pragma unroll
+        for (int k8 = 0; k8 < KSMAX / 4; ++k8) {
+          if (k8 * 8 < dim) {
+#pragma unroll
+            for (int k = k8 * 8; k < k8 * 8 + 8; ++k) {
+              const float v = zr[k];                   // (rows past n_tokens were staged as zeros)
+              zz = fmaf(v, v, zz);
+              if ((k & 1) == fh) az[k >> 1] = v;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();                                   // the tiles take the buffers over
+  }
+  float zzr[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) zzr[e] = __shfl(zz, (e & 3) + 8 * (e >> 2) + 4 * fh);
+  const float inf = __uint_as_float(0x7f800000u);
+  float best[16];
+  int besti[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { best[e] = inf; besti[e] = 0; }
+  const int jbeg = blockIdx.y * codes_per_split;
+  int jend = jbeg + codes_per_split;
+  if (jend > n_codes) jend = n_codes;
+  // tile staging through registers: the next tile's global loads are in flight under this tile's MFMAs
+  const int scode = tid >> 3, sq = tid & 7;
+  float4 pf[NCH];
+  float pe = 0.f;
+  auto fetch = [&](int j0) {
+    const bool row = j0 + scode < jend;
+    const float* src = cb + (int64_t)(row ? j0 + scode : 0) * dim;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) {
+      const int q = sq + 8 * u;
+      pf[u] = (row && q < NQ) ? *(const float4*)(src + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    pe = (tid < CT && j0 + tid < jend) ? ee_all[j0 + tid] : inf;
+  };
+  auto stash = [&](int buf) {                       // de-interleave: k = 4q, 4q + 2 -> parity 0; 4q + 1, 4q + 3 -> parity 1
+    float* dst = lds + (buf * CT + scode) * RS;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) {
+      const int q = sq + 8 * u;
+      if (q < NQ) {
+        *(float2*)(dst + 2 * q) = make_float2(pf[u].x, pf[u].z);
+        *(float2*)(dst + KS + 2 * q) = make_float2(pf[u].y, pf[u].w);
+      }
+    }
+    if (tid < CT) tee[buf * CT + tid] = pe;
+  };
+  auto load_b = [&](float (&bz)[16], const float* bsrc, int s0) {   // components s0 ... s0 + 15 of this lane's parity (those below KS)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (s0 + q * 4 < KS) {
+        const float4 v = *(const float4*)(bsrc + s0 + q * 4);
+        bz[q * 4] = v.x; bz[q * 4 + 1] = v.y; bz[q * 4 + 2] = v.z; bz[q * 4 + 3] = v.w;
+      }
+    }
+  };
+  if (jbeg < jend) { fetch(jbeg); stash(0); }
+  __syncthreads();
+  int buf = 0;
+  for (int j0 = jbeg; j0 < jend; j0 += CT, buf ^= 1) {
+    const bool more = j0 + CT < jend;
+    if (more) fetch(j0 + CT);
+    const float* bsrc = lds + (buf * CT + fr) * RS + fh * KS;
+    float bz[2][16];
+    load_b(bz[0], bsrc, 0);
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c * 16 < KS) {
+        if (c + 1 < NCH) load_b(bz[(c + 1) & 1], bsrc, (c + 1) * 16);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          if (c * 16 + g * 4 < KS) {
+#pragma unroll
+            for (int sidx = g * 4; sidx < g * 4 + 4; ++sidx) acc = mfma_32x32x2_f32(az[c * 16 + sidx], bz[c & 1][sidx], acc);
+          }
+        }
+      }
+    }
+    const float ee = tee[buf * CT + fr];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float d = (zzr[e] - 2.f * acc[e]) + ee;
+      const bool lt = d < best[e];
+      best[e] = lt ? d : best[e];
+      besti[e] = lt ? j0 : besti[e];
+    }
+    if (more) stash(buf ^ 1);                        // (buffer buf ^ 1 was last read one tile ago: behind the barrier below)
+    __syncthreads();
+  }
+  vq_mfma_split_store(best, besti, fr, fh, tok0, n_tokens, pmin, pidx);
+}
+
+// |e_j|^2 and the split merge for a `dim` that is a kernel argument (the wide search).  The merge runs one thread per element of
+// zq, so that the rows are written coalesced: every thread of a token repeats the (short) scan over the splits.
+__global__ __launch_bounds__(256) void vq_code_norms_any_kernel(const float* __restrict__ cb, int n_codes, int dim, float* __restrict__ ee) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_codes) return;
+  float acc = 0.f;
+#pragma unroll 8
+  for (int k = 0; k < dim; ++k) { const float v = cb[(int64_t)j * dim + k]; acc = fmaf(v, v, acc); }
+  ee[j] = acc;
+}
+__global__ __launch_bounds__(256) void vq_finalize_any_kernel(const float* __restrict__ pmin, const int* __restrict__ pidx,
+                                                               const float* __restrict__ cb, int64_t n_tokens, int dim, int nsplit,
+                                                               int64_t* __restrict__ idx, float* __restrict__ zq, float* __restrict__ min_dist) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_tokens * dim) return;
+  const int64_t tok = i / dim;
+  const int k = (int)(i - tok * dim);
+  float best = pmin[tok];
+  int bi = pidx[tok];
+  for (int s = 1; s < nsplit; ++s) {
+    const float d = pmin[(int64_t)s * n_tokens + tok];
+    if (d < best) { best = d; bi = pidx[(int64_t)s * n_tokens + tok]; }
+  }
+  if (k == 0) {
+    idx[tok] = bi;
+    if (min_dist) min_dist[tok] = best;
+  }
+  if (zq) zq[i] = cb[(int64_t)bi * dim + k];
+}
+
 template <int D>
 __global__ void vq_finalize_kernel(const float* __restrict__ pmin, const int* __restrict__ pidx, const float* __restrict__ cb,
                                    int64_t n_tokens, int nsplit, int64_t* __restrict__ idx, float* __restrict__ zq,
@@ -326,26 +571,36 @@ extern "C" int vq_vq_nearest_fwd(const float* z, const float* codebook, int64_t 
   VQ_REQUIRE(z && codebook && idx && workspace, VQ_ERR_INVALID, "vq_vq_nearest_fwd: null pointer");
   VQ_REQUIRE(n_tokens > 0 && n_codes > 0, VQ_ERR_INVALID, "vq_vq_nearest_fwd: empty problem");
   VQ_REQUIRE(ws_bytes >= vq_vq_workspace(n_tokens, n_codes), VQ_ERR_WORKSPACE, "vq_vq_nearest_fwd: workspace too small");
+  VQ_REQUIRE(dim == 4 || (dim >= 8 && dim <= 256 && dim % 8 == 0), VQ_ERR_UNSUPPORTED,
+             "vq_vq_nearest_fwd: unsupported code dim %d (4, or a multiple of 8 from 8 to 256)", dim);
   const int nsplit = vq_nsplit(n_tokens, n_codes);
-  const int cps = (int)(vq_ceil_div(vq_ceil_div(n_codes, nsplit), VQ_TILE) * VQ_TILE);
-  const int ns = (int)vq_ceil_div(n_codes, cps);
   float* pmin = (float*)workspace;
   int* pidx = (int*)(pmin + (size_t)nsplit * n_tokens);
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)vq_ceil_div(n_tokens, 256), ns);
   const unsigned fb = (unsigned)vq_ceil_div(n_tokens, 256);
-  // code dimensions 8 ... 64 (multiples of 4) on the fp32 MFMA (128 tokens per block, same code splits); 4 keeps the VALU kernel
-  // (two blocks per CU — each a long run of code tiles, so the per-block prologue and merge are amortised — and never more splits
-  //  than the workspace was sized for)
+  if (dim == 4) {                                    // the VALU kernel
+    const int cps = (int)(vq_ceil_div(vq_ceil_div(n_codes, nsplit), VQ_TILE) * VQ_TILE);
+    const int ns = (int)vq_ceil_div(n_codes, cps);
+    hipLaunchKernelGGL((vq_nearest_kernel<4>), dim3(fb, ns), dim3(256), 0, s, z, codebook, n_tokens, n_codes, cps, pmin, pidx);
+    VQ_CHECK_LAUNCH("vq_vq_nearest_fwd");
+    hipLaunchKernelGGL((vq_finalize_kernel<4>), dim3(fb), dim3(256), 0, s, (const float*)pmin, (const int*)pidx, codebook, n_tokens, ns,
+                       idx, zq, min_dist);
+    VQ_CHECK_LAUNCH("vq_vq_nearest_fwd(finalize)");
+    return VQ_OK;
+  }
+  // every other code dimension on the fp32 MFMA, 128 tokens per block: 8, 16, 32, 64 in vq_nearest_mfma_kernel<D>, the rest in the
+  // wide kernel (two blocks per CU — each a long run of code tiles, so the per-block prologue and merge are amortised — and never
+  // more splits than the workspace was sized for: its size does not depend on `dim`)
   int64_t msplit = vq_ceil_div(vq_mfma_blocks(), vq_ceil_div(n_tokens, 128));
   if (msplit > nsplit) msplit = nsplit;
   const int mcps = (int)(vq_ceil_div(vq_ceil_div(n_codes, msplit), VQ_TILE) * VQ_TILE);
   const int mns = (int)vq_ceil_div(n_codes, mcps);
   const dim3 mgrid((unsigned)vq_ceil_div(n_tokens, 128), mns);
   float* ee = (float*)(pidx + (size_t)nsplit * n_tokens);
+  const dim3 ngrid((unsigned)vq_ceil_div(n_codes, 256));
 #define VQ_NM(Dv)                                                                                                  \
   do {                                                                                                             \
-    hipLaunchKernelGGL((vq_code_norms_kernel<Dv>), dim3((unsigned)vq_ceil_div(n_codes, 256)), dim3(256), 0, s, codebook, n_codes, ee); \
+    hipLaunchKernelGGL((vq_code_norms_kernel<Dv>), ngrid, dim3(256), 0, s, codebook, n_codes, ee);                 \
     hipLaunchKernelGGL((vq_nearest_mfma_kernel<Dv>), mgrid, dim3(256), 0, s, z, codebook, (const float*)ee, n_tokens, n_codes, mcps, pmin, pidx); \
     VQ_CHECK_LAUNCH("vq_vq_nearest_fwd(mfma)");                                                                    \
     hipLaunchKernelGGL((vq_finalize_kernel<Dv>), dim3(fb), dim3(256), 0, s, (const float*)pmin, (const int*)pidx, codebook, \
@@ -358,21 +613,22 @@ extern "C" int vq_vq_nearest_fwd(const float* z, const float* codebook, int64_t 
   if (dim == 8) VQ_NM(8);
   if (dim == 64) VQ_NM(64);
 #undef VQ_NM
-#define VQ_NN(Dv)                                                                                                  \
-  do {                                                                                                             \
-    hipLaunchKernelGGL((vq_nearest_kernel<Dv>), grid, dim3(256), 0, s, z, codebook, n_tokens, n_codes, cps, pmin, pidx); \
-    VQ_CHECK_LAUNCH("vq_vq_nearest_fwd");                                                                          \
-    hipLaunchKernelGGL((vq_finalize_kernel<Dv>), dim3(fb), dim3(256), 0, s, (const float*)pmin, (const int*)pidx, codebook, \
-                       n_tokens, ns, idx, zq, min_dist);                                                           \
-    VQ_CHECK_LAUNCH("vq_vq_nearest_fwd(finalize)");                                                                \
-  } while (0)
-  if (dim == 32) VQ_NN(32);
-  else if (dim == 16) VQ_NN(16);
-  else if (dim == 8) VQ_NN(8);
-  else if (dim == 4) VQ_NN(4);
-  else if (dim == 64) VQ_NN(64);
-  else { vq_set_error("vq_vq_nearest_fwd: unsupported code dim %d (4,8,16,32,64)", dim); return VQ_ERR_UNSUPPORTED; }
-#undef VQ_NN
+  const size_t lds = vq_wide_lds_bytes(dim);
+  static_assert(vq_wide_lds_bytes(248) <= 64 * 1024 && vq_wide_lds_bytes(256) <= 160 * 1024, "only dim 256 needs the LDS opt-in");
+  if (lds > 64 * 1024) VQ_RESERVE_LDS(vq_nearest_wide_kernel<256>, vq_wide_lds_bytes(256), "vq_vq_nearest_fwd(wide)");
+  hipLaunchKernelGGL(vq_code_norms_any_kernel, ngrid, dim3(256), 0, s, codebook, n_codes, dim, ee);
+#define VQ_NW(Dv) \
+  case Dv: hipLaunchKernelGGL((vq_nearest_wide_kernel<Dv>), mgrid, dim3(256), lds, s, z, codebook, (const float*)ee, n_tokens, n_codes, mcps, pmin, pidx); break;
+  switch (dim) {
+    VQ_NW(24) VQ_NW(40) VQ_NW(48) VQ_NW(56) VQ_NW(72) VQ_NW(80) VQ_NW(88) VQ_NW(96) VQ_NW(104) VQ_NW(112) VQ_NW(120) VQ_NW(128)
+    VQ_NW(136) VQ_NW(144) VQ_NW(152) VQ_NW(160) VQ_NW(168) VQ_NW(176) VQ_NW(184) VQ_NW(192) VQ_NW(200) VQ_NW(208) VQ_NW(216)
+    VQ_NW(224) VQ_NW(232) VQ_NW(240) VQ_NW(248) VQ_NW(256)
+  }
+#undef VQ_NW
+  VQ_CHECK_LAUNCH("vq_vq_nearest_fwd(wide)");
+  hipLaunchKernelGGL(vq_finalize_any_kernel, dim3((unsigned)vq_ceil_div(n_tokens * dim, 256)), dim3(256), 0, s, (const float*)pmin,
+                     (const int*)pidx, codebook, n_tokens, dim, mns, idx, zq, min_dist);
+  VQ_CHECK_LAUNCH("vq_vq_nearest_fwd(finalize)");
   return VQ_OK;
 }
 
