@@ -364,11 +364,19 @@ int vq_gan_disc_loss(const float* real, const float* fake, int64_t n, int disc_t
 typedef struct VqAdamTensor {
   float* p; const float* g; float* m; float* v;
   int64_t n;
-} VqAdamTensor;
+  float* ema;              /* NULL: this tensor keeps no shadow.  Else [n] fp32, must not alias p / g / m / v */
+  const float* ema_decay;  /* DEVICE scalar d in [0, 1]; read by the launch (not by the host call) when ema != NULL */
+} VqAdamTensor;            /* 56 bytes (ABI 12; before: 40, without the two trailing fields) */
 /* `table` is a DEVICE array of n_tensors descriptors; `chunk_offsets` a DEVICE int64 array with
  * n_tensors+1 prefix sums of ceil(n/chunk). */
+/* Weight EMA (ABI 12): an entry with ema != NULL keeps an exponential moving average of its parameters.  After the AdamW update of
+ * an element the same launch computes, in fp32,  ema += (p_new - ema) * (1 - d)  (torch's lerp_ form, like the m update), where
+ * p_new is exactly the value stored to p and d = *ema_decay is read on the device: a decay warm-up rewrites one device float and
+ * never the table, and needs no host sync.  A table may mix entries with and without a shadow; an entry without one is updated by
+ * the same code as before ABI 12.  The shadow is read and written 16 bytes per lane where ema is 16-byte aligned like p / g / m / v, else
+ * 4 bytes at a time; the path p / m / v take — and so their bits — never depends on the shadow's alignment. */
 /* skip_flags (may be NULL): n_flags DEVICE int32 values `skip_stride` elements apart — when any of them is non-zero the launch
- * changes NOTHING (parameters, moments): the step that produced a clipped VQ_F16 gradient (range events, see Conventions) is
+ * changes NOTHING (parameters, moments, EMA shadows — a dropped step must not pull a shadow towards parameters that did not move): the step that produced a clipped VQ_F16 gradient (range events, see Conventions) is
  * dropped on the device, no host sync.  The caller keeps its own step counter in line (bias corrections) when it reads the flags. */
 int vq_adamw_multi(const VqAdamTensor* table, const int64_t* chunk_offsets, int n_tensors,
                    int64_t total_chunks, int chunk, float lr, float wd, float beta1, float beta2,

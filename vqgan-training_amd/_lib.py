@@ -16,7 +16,7 @@ VQ_BF16 = 0
 VQ_F32 = 1
 VQ_F16 = 2
 VQ_F16X2 = 3      # two binary16 pieces per value (hi, lo), carried by torch.complex32 tensors: 4 bytes per element, same shapes
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libvqhip.so")
@@ -40,7 +40,10 @@ class VqGnBwdFuse(C.Structure):
 
 
 class VqAdamTensor(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+    """Mirror of `struct VqAdamTensor` (include/vqhip.h); ema = NULL: no shadow (ema_decay: a DEVICE float)."""
+
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("ema", C.c_void_p), ("ema_decay", C.c_void_p)]
 
 
 class VqPackJob(C.Structure):

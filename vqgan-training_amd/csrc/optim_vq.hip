@@ -2,16 +2,94 @@
 //
 // AdamW: vae_trainer.py:455-475 (optimizer_G two param groups, optimizer_D), stepped at
 // vae_trainer.py:659,702-704 — torch.optim.AdamW semantics, one launch for all tensors
-// (28 B/param of HBM traffic: read p,g,m,v, write p,m,v).
+// (28 B/param of HBM traffic: read p,g,m,v, write p,m,v; 36 B/param for a tensor that keeps an EMA shadow: + read and write of it).
 // VQ: not in the reference; the algorithm is pinned by oracle/vq_oracle.c.
 #include "vq_common.h"
+
+// One chunk [beg, end) of one table entry.  EMA = false is the plain update; EMA = true additionally moves the tensor's shadow
+// (VqAdamTensor::ema, include/vqhip.h) towards the value just stored to p:  ema += (p_new - ema) * (1 - d), torch's lerp_ form like the
+// m update — 8 B/param more on a value the lane already holds, against 12 B/param and a second launch for a separate pass.
+// EVEC (EMA only): the shadow is 16-byte aligned and goes 16 bytes per lane; else 4 bytes at a time.  Three instantiations of one
+// body, chosen by block-uniform branches in the kernel: the `if constexpr` arms vanish from the plain one.  (EVEC is a template
+// parameter and not a run-time flag: with a flag the compiler merged the two store arms into one — a 12-byte and a 4-byte store per
+// quad also for an aligned shadow.)
+template <bool EMA, bool EVEC, class Update>
+__device__ __forceinline__ void adamw_chunk(const VqAdamTensor& t, int64_t beg, int64_t end, float ema_w, const Update& update) {
+  auto shadow = [&](float& e, float p) { e = e + (p - e) * ema_w; };
+  // 16 bytes per lane and array, two quads per trip (8 loads in flight per lane): scalar 4-byte accesses ran this pass at 3.5-3.8 TB/s
+  // (r2 profiles).  Chunks start at multiples of 4 elements of 16-byte aligned buffers (vq_adamw_multi checks); the tail is scalar.
+  const bool aligned = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0) && (beg & 3) == 0;
+  // The shadow's 16-byte accesses need the shadow 16-byte aligned as well; one that is not goes by 4-byte accesses INSIDE the same
+  // loops: which loop p / m / v run through, and with it their bits (the compiler contracts each loop's arithmetic on its own), must
+  // not depend on where the shadow lies.
+  float* const eb = EMA ? t.ema + beg : nullptr;
+  auto load_e = [&](int64_t q) {
+    vq_f4 e;
+    if constexpr (EVEC) {
+      e = ((const vq_f4*)eb)[q];
+    } else {
+      e.x = eb[4 * q]; e.y = eb[4 * q + 1]; e.z = eb[4 * q + 2]; e.w = eb[4 * q + 3];
+    }
+    return e;
+  };
+  auto store_e = [&](int64_t q, const vq_f4& e) {
+    if constexpr (EVEC) {
+      ((vq_f4*)eb)[q] = e;
+    } else {
+      eb[4 * q] = e.x; eb[4 * q + 1] = e.y; eb[4 * q + 2] = e.z; eb[4 * q + 3] = e.w;
+    }
+  };
+  int64_t i = beg;
+  if (aligned) {
+    const int64_t nq = (end - beg) >> 2;
+    vq_f4* __restrict__ p4 = (vq_f4*)(t.p + beg);
+    const vq_f4* __restrict__ g4 = (const vq_f4*)(t.g + beg);
+    vq_f4* __restrict__ m4 = (vq_f4*)(t.m + beg);
+    vq_f4* __restrict__ v4 = (vq_f4*)(t.v + beg);
+    int64_t q = threadIdx.x;
+    for (; q + 256 < nq; q += 512) {
+      vq_f4 p0 = p4[q], g0 = g4[q], m0 = m4[q], v0 = v4[q], p1 = p4[q + 256], g1 = g4[q + 256], m1 = m4[q + 256], v1 = v4[q + 256];
+      update(g0.x, p0.x, m0.x, v0.x); update(g0.y, p0.y, m0.y, v0.y); update(g0.z, p0.z, m0.z, v0.z); update(g0.w, p0.w, m0.w, v0.w);
+      update(g1.x, p1.x, m1.x, v1.x); update(g1.y, p1.y, m1.y, v1.y); update(g1.z, p1.z, m1.z, v1.z); update(g1.w, p1.w, m1.w, v1.w);
+      p4[q] = p0; m4[q] = m0; v4[q] = v0; p4[q + 256] = p1; m4[q + 256] = m1; v4[q + 256] = v1;
+      if constexpr (EMA) {
+        vq_f4 e0 = load_e(q), e1 = load_e(q + 256);
+        shadow(e0.x, p0.x); shadow(e0.y, p0.y); shadow(e0.z, p0.z); shadow(e0.w, p0.w);
+        shadow(e1.x, p1.x); shadow(e1.y, p1.y); shadow(e1.z, p1.z); shadow(e1.w, p1.w);
+        store_e(q, e0); store_e(q + 256, e1);
+      }
+    }
+    for (; q < nq; q += 256) {
+      vq_f4 p0 = p4[q], g0 = g4[q], m0 = m4[q], v0 = v4[q];
+      update(g0.x, p0.x, m0.x, v0.x); update(g0.y, p0.y, m0.y, v0.y); update(g0.z, p0.z, m0.z, v0.z); update(g0.w, p0.w, m0.w, v0.w);
+      p4[q] = p0; m4[q] = m0; v4[q] = v0;
+      if constexpr (EMA) {
+        vq_f4 e0 = load_e(q);
+        shadow(e0.x, p0.x); shadow(e0.y, p0.y); shadow(e0.z, p0.z); shadow(e0.w, p0.w);
+        store_e(q, e0);
+      }
+    }
+    i = beg + (nq << 2);
+  }
+  for (i += threadIdx.x; i < end; i += 256) {
+    float p = t.p[i], m = t.m[i], v = t.v[i];
+    update(t.g[i], p, m, v);
+    t.p[i] = p; t.m[i] = m; t.v[i] = v;
+    if constexpr (EMA) {
+      float e = t.ema[i];
+      shadow(e, p);
+      t.ema[i] = e;
+    }
+  }
+}
 
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const VqAdamTensor* __restrict__ table,
                                                            const int64_t* __restrict__ chunk_offsets, int n_tensors,
                                                            int chunk, float lr, float wd, float beta1, float beta2,
                                                            float eps, float bc1, float bc2_sqrt, float grad_scale,
                                                            const int* __restrict__ skip_flags, int n_flags, int skip_stride) {
-  // a step whose gradients were clipped by a saturating VQ_F16 store (range events, include/vqhip.h) changes nothing: block-uniform
+  // a step whose gradients were clipped by a saturating VQ_F16 store (range events, include/vqhip.h) changes nothing — the shadow
+  // included: block-uniform
   for (int f = 0; f < n_flags; ++f)
     if (skip_flags[(int64_t)f * skip_stride] != 0) return;
   const int64_t cid = blockIdx.x;
@@ -26,6 +104,10 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const VqAdamTensor* __
   int64_t end = beg + chunk;
   if (end > t.n) end = t.n;
   const float decay = 1.f - lr * wd, step = lr / bc1;
+  // (One lambda for every loop of every instantiation below.  That p / m / v do not depend on whether a tensor keeps a shadow, or on
+  // where it lies, rests on the compiler contracting this arithmetic the same way in each copy of a loop: nothing in the language
+  // promises that — the scalar tail, for one, rounds p differently from the vector loops on gfx950 — and only the bitwise comparison
+  // with the no-shadow launch in tests/test_weight_ema.py, run on the GPU, guards it.)
   auto update = [&](float g, float& p, float& m, float& v) {
     g *= grad_scale;
     p *= decay;
@@ -34,35 +116,9 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const VqAdamTensor* __
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p -= step * (m / denom);
   };
-  // 16 bytes per lane and array, two quads per trip (8 loads in flight per lane): scalar 4-byte accesses ran this pass at 3.5-3.8 TB/s
-  // (r2 profiles).  Chunks start at multiples of 4 elements of 16-byte aligned buffers (vq_adamw_multi checks); the tail is scalar.
-  const bool aligned = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0) && (beg & 3) == 0;
-  int64_t i = beg;
-  if (aligned) {
-    const int64_t nq = (end - beg) >> 2;
-    vq_f4* __restrict__ p4 = (vq_f4*)(t.p + beg);
-    const vq_f4* __restrict__ g4 = (const vq_f4*)(t.g + beg);
-    vq_f4* __restrict__ m4 = (vq_f4*)(t.m + beg);
-    vq_f4* __restrict__ v4 = (vq_f4*)(t.v + beg);
-    int64_t q = threadIdx.x;
-    for (; q + 256 < nq; q += 512) {
-      vq_f4 p0 = p4[q], g0 = g4[q], m0 = m4[q], v0 = v4[q], p1 = p4[q + 256], g1 = g4[q + 256], m1 = m4[q + 256], v1 = v4[q + 256];
-      update(g0.x, p0.x, m0.x, v0.x); update(g0.y, p0.y, m0.y, v0.y); update(g0.z, p0.z, m0.z, v0.z); update(g0.w, p0.w, m0.w, v0.w);
-      update(g1.x, p1.x, m1.x, v1.x); update(g1.y, p1.y, m1.y, v1.y); update(g1.z, p1.z, m1.z, v1.z); update(g1.w, p1.w, m1.w, v1.w);
-      p4[q] = p0; m4[q] = m0; v4[q] = v0; p4[q + 256] = p1; m4[q + 256] = m1; v4[q + 256] = v1;
-    }
-    for (; q < nq; q += 256) {
-      vq_f4 p0 = p4[q], g0 = g4[q], m0 = m4[q], v0 = v4[q];
-      update(g0.x, p0.x, m0.x, v0.x); update(g0.y, p0.y, m0.y, v0.y); update(g0.z, p0.z, m0.z, v0.z); update(g0.w, p0.w, m0.w, v0.w);
-      p4[q] = p0; m4[q] = m0; v4[q] = v0;
-    }
-    i = beg + (nq << 2);
-  }
-  for (i += threadIdx.x; i < end; i += 256) {
-    float p = t.p[i], m = t.m[i], v = t.v[i];
-    update(t.g[i], p, m, v);
-    t.p[i] = p; t.m[i] = m; t.v[i] = v;
-  }
+  if (!t.ema) adamw_chunk<false, false>(t, beg, end, 0.f, update);
+  else if (((uintptr_t)t.ema & 15) == 0) adamw_chunk<true, true>(t, beg, end, 1.f - *t.ema_decay, update);   // (the decay: a device scalar,
+  else adamw_chunk<true, false>(t, beg, end, 1.f - *t.ema_decay, update);                                   //  read here, nowhere on the host)
 }
 
 extern "C" int vq_adamw_multi(const VqAdamTensor* table, const int64_t* chunk_offsets, int n_tensors, int64_t total_chunks,

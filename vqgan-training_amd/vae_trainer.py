@@ -205,14 +205,21 @@ class VAETrainStep:
     Augmentations (flips, flip/crop invariance, pre-LPIPS flips) follow the reference's draw order on `rng`
     (default: the `random` module, seeded by train_ddp like vae_trainer.py:374-378).  rng=False disables every
     draw — including the unconditional 50 % horizontal flip of :534 — for fixed-input parity tests and bench.py.
-    `enc_size` is the encoder input size of the area resize (:531-533; the reference hard-codes (256, 256))."""
+    `enc_size` is the encoder input size of the area resize (:531-533; the reference hard-codes (256, 256)).
+
+    Weight EMA (not in the reference): with `ema_decay` > 0 optimizer_G keeps an exponential moving average of every generator
+    parameter, updated inside its AdamW launch (optim.FusedAdamW; `ema_warmup`: decay min(ema_decay, (1 + t) / (10 + t))), and
+    `ema_weights()` swaps it in for evaluation and checkpoints.  A gradient-trained codebook sits in optimizer_G's main group and
+    gets a shadow like every other generator parameter; the codebook of an `ema=True` quantizer is no optimizer parameter: it has
+    no shadow and the swap leaves it alone.  The discriminator keeps no shadow."""
 
     def __init__(self, vae: VAE, lpips: LPIPS, discriminator: PatchDiscriminator | None = None, *,
                  do_ganloss=False, disc_type="bce", use_lecam=False, learning_rate_vae=1e-5, learning_rate_disc=2e-4,
                  vae_ch=256, max_steps=1000, warmup_steps=200, do_clamp=False, clamp_th=8.0, sync_vae_grads=True,
                  bucket_bytes=32 << 20, on_backward=None, rng=False, enc_size=None, flip_invariance=False,
                  crop_invariance=False, augment_before_perceptual_loss=False, decoder_also_perform_hr=False,
-                 downscale_factor=16, quantizer=None, single_rank_collectives=False, on_d_backward=None, gradnorm_dp_chunks=1):
+                 downscale_factor=16, quantizer=None, single_rank_collectives=False, on_d_backward=None, gradnorm_dp_chunks=1,
+                 ema_decay=0.0, ema_warmup=False):
         self.vae, self.lpips, self.disc = vae, lpips, discriminator
         self.quantizer = quantizer                # config 5: VectorQuantizer in place of `vae.reg` (not in the reference, F1)
         self.rng = random if rng is None else rng
@@ -238,7 +245,7 @@ class VAETrainStep:
         self.optimizer_G = FusedAdamW(
             [{"params": [p for n, p in named if "conv_in" not in n], "lr": learning_rate_vae / vae_ch},
              {"params": [p for n, p in named if "conv_in" in n], "lr": 1e-4}],
-            weight_decay=1e-3, betas=(0.9, 0.95))
+            weight_decay=1e-3, betas=(0.9, 0.95), ema_decay=ema_decay if ema_decay else None, ema_warmup=ema_warmup)
         self._base_lrs = [g["lr"] for g in self.optimizer_G.param_groups]
         self.reducer_G = BucketedGradReducer(self.optimizer_G._flat, bucket_bytes, enabled=sync_vae_grads,
                                              single_rank_ok=single_rank_collectives)
@@ -394,8 +401,32 @@ class VAETrainStep:
                 self._fwd_sat_polls.pop(region, None)
         return moved
 
+    def ema_weights(self):
+        """Context manager: the generator's parameters (and packed conv operands) hold the EMA shadow inside (FusedAdamW.ema_weights)."""
+        return self.optimizer_G.ema_weights()
+
+    def load_ema(self, path: str | None) -> bool:
+        """The shadow from a checkpoint file `save_checkpoint` wrote inside `ema_weights()` — a strict load into the swapped-in
+        parameters, which the exit of the context writes back to the shadow's place.  No file (None, or missing): the shadow
+        starts from the current parameters, with a log line.  Returns whether a file was loaded."""
+        opt = self.optimizer_G
+        if path is None or not os.path.exists(path):
+            with torch.no_grad():
+                for f in opt._flat:
+                    f.flat_ema.copy_(f.flat_p)
+            logging.getLogger(__name__).info(f"no EMA checkpoint{'' if path is None else ' at ' + path}: the EMA weights start from the loaded weights")
+            return False
+        quantizer = self.quantizer if (self.quantizer is not None and not self._ema_vq) else None
+        with opt.ema_weights():
+            # (an EMA quantizer's codebook has no shadow: the `quantizer.*` keys of the file are dropped, its state stays as loaded)
+            load_checkpoint(self.vae, path, quantizer=quantizer)
+            with torch.no_grad():
+                for f in opt._flat:
+                    f.flat_ema.copy_(f.flat_p)
+        return True
+
     def state_snapshot(self) -> dict:
-        """Everything a step changes — parameters, AdamW moments and step counts of both optimizers, the LR schedule's counter, the
+        """Everything a step changes — parameters, AdamW moments and step counts of both optimizers (the weight EMA inside G's), the LR schedule's counter, the
         LeCam anchors, the random streams the step draws from — so that `state_restore` puts the run back exactly here (bench.py:
         the rehearsal that measures the loss scales the timed steps need)."""
         return {"G": self.optimizer_G.snapshot(moments=True),
@@ -687,6 +718,12 @@ def save_checkpoint(vae: VAE, path: str, ddp_prefix: bool = True, quantizer=None
     torch.save(sd, path)
 
 
+def ema_checkpoint_path(path: str) -> str:
+    """`<name>_ema<ext>`: the sibling file that holds the EMA weights of checkpoint `path`."""
+    root, ext = os.path.splitext(path)
+    return root + "_ema" + ext
+
+
 def export_bf16_safetensors(vae: VAE, path: str) -> None:
     """The release format of README.hf.md:38-40 / tester_upload.sh (fal/AuraEquiVAE `*_bf16.pt`): a safetensors file of
     bf16 tensors with un-prefixed keys, loadable by `VAE(...).bfloat16().load_state_dict(load_file(path))`."""
@@ -819,6 +856,8 @@ def _build_cli():
     @click.option("--precision", type=str, default=None, help="default: ref (ref_vq with a quantizer); ref | ref2 | ref3 | ref_vq | bf16 | fp32 | fp32x3 | fp32x6 | f16x3 (PRECISION_POLICIES)")
     @click.option("--sync_vae_grads", type=bool, default=True, help="False = reference behaviour (SURVEY F2)")
     @click.option("--backend", type=str, default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm)")
+    @click.option("--ema_decay", type=float, default=0.0, help="decay of the generator's weight EMA (0 = off); evaluation and <ckpt>_ema files use it")
+    @click.option("--ema_warmup", is_flag=True, help="EMA decay min(ema_decay, (1 + t) / (10 + t)) over the applied updates t")
     @click.option("--vgg_backbone_path", type=str, default=None,
                   help="torchvision vgg16 state dict (vgg16-397923af.pth) for LPIPS / PatchDiscriminator; default: $VQ_VGG16_WEIGHTS or ./vgg16*.pth")
     def train_ddp(**kw):
@@ -835,7 +874,7 @@ def run_training(*, dataset_url="", test_dataset_url="", num_epochs=2, batch_siz
                  flip_invariance=False, do_compile=False, use_wavelet=False, augment_before_perceptual_loss=False,
                  downscale_factor=16, use_lecam=False, disc_type="bce", synthetic=True, precision=None,
                  sync_vae_grads=True, backend="nccl", log_every=5, vgg_backbone_path=None, train_batches=None,
-                 test_batches=None, quantizer=None):
+                 test_batches=None, quantizer=None, ema_decay=0.0, ema_warmup=False):
     """train_ddp body (vae_trainer.py:339-912) for the hot path: setup, step loop, device-side logging.
     Input: `train_batches` / `test_batches` = any iterable (list, generator, DataLoader, a webdataset pipeline built by the
     caller) of [-1, 1] NCHW float batches, or (batch, label) pairs as the reference's loader yields (vae_trainer.py:530:
@@ -843,7 +882,10 @@ def run_training(*, dataset_url="", test_dataset_url="", num_epochs=2, batch_siz
     until `max_steps`; every rank must be handed its own shard (the reference splits by node and worker inside webdataset,
     vae_trainer.py:119-140 — that I/O layer is out of scope here).  Without iterables: `--synthetic True` (default)
     feeds uniform-noise batches resident in HBM; `--synthetic False` needs the iterables.
-    `quantizer`: a VectorQuantizer in place of `vae.reg` (config 5): trained, evaluated and checkpointed with the VAE."""
+    `quantizer`: a VectorQuantizer in place of `vae.reg` (config 5): trained, evaluated and checkpointed with the VAE.
+    `ema_decay` > 0 (`--ema_decay`, `--ema_warmup`): the generator's weight EMA (VAETrainStep) — the logged reconstructions are the
+    EMA model's, every checkpoint `X.pt` is followed by `X_ema.pt` in the same format (save_checkpoint inside `ema_weights()`), and
+    `--load_path X.pt` resumes the shadow from `X_ema.pt` when that file exists."""
     if not synthetic and train_batches is None:
         raise NotImplementedError("no input: pass train_batches=<iterable of [-1,1] NCHW batches> to run_training (the reference's "
                                   "webdataset pipeline, vae_trainer.py:119-140, is out of scope) or use --synthetic True")
@@ -896,11 +938,15 @@ def run_training(*, dataset_url="", test_dataset_url="", num_epochs=2, batch_siz
                         max_steps=max_steps, do_clamp=do_clamp, clamp_th=clamp_th, sync_vae_grads=sync_vae_grads,
                         rng=None, enc_size=(vae_resolution, vae_resolution), flip_invariance=flip_invariance, crop_invariance=crop_invariance,
                         augment_before_perceptual_loss=augment_before_perceptual_loss,
-                        decoder_also_perform_hr=decoder_also_perform_hr, downscale_factor=downscale_factor, quantizer=quantizer)
+                        decoder_also_perform_hr=decoder_also_perform_hr, downscale_factor=downscale_factor, quantizer=quantizer,
+                        ema_decay=ema_decay, ema_warmup=ema_warmup)
     logger = logging.getLogger(__name__)
     logger.setLevel(logging.INFO)
     if rank == 0 and not logger.handlers:
         logger.addHandler(logging.StreamHandler())
+    use_ema = bool(ema_decay)
+    if use_ema and load_path is not None:                  # every rank reads the same file (or none): the shadows start from the same bits
+        step.load_ema(ema_checkpoint_path(load_path))
     gen = torch.Generator(device=device).manual_seed(42 + rank)
     img_res = vae_resolution * (2 if decoder_also_perform_hr else 1)
     test_gen = torch.Generator(device=device).manual_seed(4242)
@@ -933,11 +979,18 @@ def run_training(*, dataset_url="", test_dataset_url="", num_epochs=2, batch_siz
         res = step(x)
         # vae_trainer.py:805-910: the reference tests `global_step % n == 1` AFTER incrementing the counter
         if evaluate_every_n_steps > 0 and (global_step + 1) % evaluate_every_n_steps == 1 and rank == 0:
-            evaluate(vae, eval_batches, do_clamp=do_clamp, clamp_th=clamp_th, flip_invariance=flip_invariance,
-                     decoder_also_perform_hr=decoder_also_perform_hr, enc_size=(vae_resolution, vae_resolution), quantizer=quantizer)
+            eval_kw = dict(do_clamp=do_clamp, clamp_th=clamp_th, flip_invariance=flip_invariance,
+                           decoder_also_perform_hr=decoder_also_perform_hr, enc_size=(vae_resolution, vae_resolution), quantizer=quantizer)
             ckpt = f"./ckpt/{run_name}/vae_epoch_0_step_{global_step + 1}.pt"
+            if not use_ema:
+                evaluate(vae, eval_batches, **eval_kw)
             save_checkpoint(vae, ckpt, quantizer=quantizer)
             logger.info(f"Saved checkpoint to {ckpt}")
+            if use_ema:                                    # ONE swap: the logged grids are the EMA model's, and so is the second file —
+                with step.ema_weights():                   # the same writer, the same keys and layout: any loader of `ckpt` reads it
+                    evaluate(vae, eval_batches, **eval_kw)
+                    save_checkpoint(vae, ema_checkpoint_path(ckpt), quantizer=quantizer)
+                logger.info(f"Saved EMA checkpoint to {ema_checkpoint_path(ckpt)}")
         if global_step % log_every == 0:                   # the only host syncs: every `log_every` steps (every rank: the poll may re-calibrate)
             rec = logged_scalars(res, step, do_ganloss) if rank == 0 else {}
             rec["time_taken_till_step"] = time.time() - t0
